@@ -11,7 +11,12 @@ parse's frame classes: k_decode_st (stereo LPC <= 8, C2), k_decode_sw (24-bit st
 k_decode<8|16|32> (the rest), or k_decode_sys (the systolic LPC restore) for launches too small
 to fill the chip with one subframe per lane (C5, the reader).
 
-The other 1-GPU configs are side legs of the same line (rank 0, N = 1 only; `--legs`):
+A plain run sets up, warms up, times the K steps, checks what it timed (`bitexact`: the metric is
+of bit-exact PCM), writes `--dump-outputs` and prints the line.  Everything below that takes a run
+of its own -- the side legs, cpu_baseline, indexer, reader, pcie_inclusive, the C5 flow at N > 1 --
+is measured only with `--full`.
+
+The other 1-GPU configs are side legs of the same line (`--full`, rank 0, N = 1 only; `--legs`):
   C3  96 kHz/24-bit stereo, LPC-12, bs 8192, wasted bits + mid/side -> FLACFileReader 3-byte PCM
   C4  mixed CONSTANT/VERBATIM/FIXED/LPC, variable bs 192-16384, 16-bit stereo -> FLACDecoder PCM
   C5  8 distinct 192 kHz/24-bit 8-channel LPC-32 files (469 frames each, c5_job at one rank)
@@ -32,7 +37,11 @@ cpu_baseline = the CPU restatement (oracle/: libFLAC 1.2.1 decode + the C# pack 
                every host core this process may use (os.sched_getaffinity), plus a 1-thread figure,
                on a bounded sample of the same frames.
 
-    python bench.py [--gpus N --steps K --warmup W --batches B --config C2|C3|C4|C5 --legs C3,C4,C5]
+`--dump-outputs DIR` writes what the last timed step left in the caller's buffers (dump_outputs):
+the same arguments give the same input bytes, so two builds compare file for file.
+
+    python bench.py [--gpus N --steps K --warmup W --batches B --config C2|C3|C4|C5 --dump-outputs DIR]
+    python bench.py --full [--legs C3,C4,C5 ...]
     torchrun --nproc-per-node N bench.py --gpus N ...   (or: python bench.py --gpus N, which starts the
                                                          N rank processes itself)
 """
@@ -86,7 +95,12 @@ def parse_args():
                     help="copies decoded per step (0: the config's default; C2: 1024 = eight rounds of "
                          "k_decode_st waves, DESIGN.md section 5; C5: files in the job)")
     ap.add_argument("--frames", type=int, default=0, help="frames per batch (0: the config's)")
-    ap.add_argument("--legs", default="C3,C4,C5", help="side legs at N = 1 (comma list, '' for none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: side legs, CPU baselines, indexer, "
+                         "reader, PCIe-inclusive rate, the C5 flow at N > 1 (off: the timed steps and their check only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's PCM and frame records as DIR/<name>.npy")
+    ap.add_argument("--legs", default="C3,C4,C5", help="--full: side legs at N = 1 (comma list, '' for none)")
     ap.add_argument("--leg-steps", type=int, default=3)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline time budget (headline)")
     ap.add_argument("--leg-cpu-seconds", type=float, default=3.0, help="CPU baseline time budget per leg")
@@ -228,6 +242,49 @@ def pack_reference(pcm: np.ndarray, fmt: str, bps: int) -> bytes:
     if bps == 16:
         return pcm.astype("<i2").tobytes()
     return np.ascontiguousarray(pcm.astype("<i4")).view(np.uint8).reshape(-1, 4)[:, :3].tobytes()
+
+
+# --dump-outputs: a leading piece plus seeded runs of the PCM and of the frame records, 44 MB at most
+DUMP_HEAD, DUMP_RUNS, DUMP_RUN = 8 << 20, 32, 1 << 16   # PCM samples: 32 MB + 8 MB as float32
+DUMP_FHEAD, DUMP_FRUN = 1 << 15, 1 << 10                # frame records: 2 MB + 2 MB as float64
+DUMP_INFO_FIELDS = ("status", "err", "blocksize", "channels", "bps", "out_sample", "crc16_calc", "crc_ok")
+
+
+def dump_pieces(n: int, head: int, run: int, seed: int) -> list:
+    """[0, head) and DUMP_RUNS seeded runs of `run` items of [0, n): the same pieces for the same n."""
+    pieces = [(0, min(n, head))]
+    if n > head:
+        rng = np.random.default_rng(seed)
+        pieces += [(int(a), int(a) + min(run, n)) for a in sorted(rng.integers(0, max(1, n - run + 1), DUMP_RUNS))]
+    return pieces
+
+
+def unpack_pcm(raw: np.ndarray, width: int) -> np.ndarray:
+    """Little-endian `width`-byte PCM samples as floats that hold them exactly."""
+    if width == 2:
+        return raw.view("<i2").astype(np.float32)
+    if width == 4:
+        return raw.view("<i4").astype(np.float64)
+    b = raw.reshape(-1, 3).astype(np.int32)
+    v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+    return ((v ^ 0x800000) - 0x800000).astype(np.float32)
+
+
+def dump_outputs(path, libflac, d_out, nbytes, width, d_info, nframes, tag=""):
+    """What a caller of the timed path holds after its last step, as float .npy files:
+    pcm_head (the first DUMP_HEAD samples of the output buffer), pcm_sample (DUMP_RUNS seeded runs
+    of DUMP_RUN samples over the whole buffer, in buffer order) and frame_info (one row per frame
+    record, columns DUMP_INFO_FIELDS: the first DUMP_FHEAD records, then seeded runs of them)."""
+    os.makedirs(path, exist_ok=True)
+    pcm = [unpack_pcm(d_out[a * width:b * width].cpu().numpy(), width)
+           for a, b in dump_pieces(nbytes // width, DUMP_HEAD, DUMP_RUN, 0xF1AC)]
+    np.save(os.path.join(path, f"pcm_head{tag}.npy"), pcm[0])
+    np.save(os.path.join(path, f"pcm_sample{tag}.npy"), np.concatenate(pcm[1:]) if pcm[1:] else pcm[0][:0])
+    R = libflac.FRAME_INFO_BYTES
+    info = np.concatenate([libflac.info_array(d_info[a * R:b * R].cpu().numpy())
+                           for a, b in dump_pieces(nframes, DUMP_FHEAD, DUMP_FRUN, 0xF1AD)])
+    np.save(os.path.join(path, f"frame_info{tag}.npy"),
+            np.stack([info[f].astype(np.float64) for f in DUMP_INFO_FIELDS], axis=1))
 
 
 class Workload:
@@ -742,7 +799,9 @@ def c5_job(args, torch, dist, dev, libflac, synth, dec, world, rank, files=None,
     alg = comp + nsmp * stride
     return {"samples": samples, "t_dec": t_dec, "t_all": t_all, "t_ovl": t_ovl, "t_grp": t_grp, "t_launch": t_launch, "ok": ok,
             "t_parse": t_parse, "t_decode": t_decode,
-            "files": F, "alg_bytes_rank": alg, "frames_rank": nframes}
+            "files": F, "alg_bytes_rank": alg, "frames_rank": nframes,
+            # what the caller holds after the last step (--dump-outputs): rank 0's gathered PCM, this rank's records
+            "pcm": gathered, "pcm_width": stride // p0.channels, "info": d_info}
 
 
 def c5_summary(r, args, world, steps=None):
@@ -818,6 +877,9 @@ def main():
                                 "files": r["files"],
                                 "parallelism": f"files sharded per rank x{world} + RCCL gather to rank 0"}})
         if rank == 0:
+            if args.dump_outputs and r["pcm"] is not None:
+                dump_outputs(args.dump_outputs, libflac, r["pcm"], r["pcm"].numel(), r["pcm_width"], r["info"],
+                             r["frames_rank"])
             js = json.dumps(line)
             print(js, flush=True)
             if args.out:
@@ -840,6 +902,9 @@ def main():
         o = torch.tensor([1 if ok else 0], device=dev)
         dist.all_reduce(o, op=dist.ReduceOp.MIN)
         ok = bool(o.item())
+    if args.dump_outputs:  # every rank its own buffers
+        dump_outputs(args.dump_outputs, libflac, wl.d_out, wl.pcm1 * wl.B, wl.stride // wl.p.channels, wl.d_info,
+                     wl.nframes, tag=f"_rank{rank}" if world > 1 else "")
     step_ms = elapsed / args.steps * 1e3
     samples = wl.samples
     if world > 1:  # every rank's own count (its stream's samples)
@@ -867,6 +932,7 @@ def main():
         "bitexact": ok,
         "roofline": roofline(wl.alg_bytes, t_decode, t_parse, step_ms, measured_traffic(cfg, B, wl.nf1)),
         "kernels_sha": kernels_sha(),
+        "full": args.full,
     }
     if args.stats and rank == 0:
         import ctypes
@@ -898,21 +964,21 @@ def main():
                         "k_decode_ms": round(sum(a.elapsed_time(b) for a, b in de) / len(de), 4)})
         dec.L.bnflac_debug_set_ablate(0)
         line["ablation"] = abl
-    if rank == 0 and not args.no_index:
+    if rank == 0 and args.full and not args.no_index:
         line["indexer"] = index_leg(wl)
-    if rank == 0 and not args.no_reader:
+    if rank == 0 and args.full and not args.no_reader:
         line["reader"] = reader_leg(wl)
-    if rank == 0 and not args.no_pcie:
+    if rank == 0 and args.full and not args.no_pcie:
         line["pcie_inclusive"] = pcie_inclusive(wl)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         sys.stdout.flush()
         line["cpu_baseline"] = cpu_leg(wl, args.cpu_seconds, args.cpu_threads)
-    legs = [x for x in args.legs.split(",") if x and x != cfg] if world == 1 else []
+    legs = [x for x in args.legs.split(",") if x and x != cfg] if args.full and world == 1 else []
     if legs:
         del wl
         torch.cuda.empty_cache()
         line["legs"] = {x: leg(x, args, torch, dev, libflac, synth, dec, stream) for x in legs}
-    elif world > 1 and not args.no_c5_flow:
+    elif args.full and world > 1 and not args.no_c5_flow:
         # BASELINE config 5 at N GPUs: the files sharded over the ranks, each rank indexing and
         # decoding its own, then the gather of every rank's PCM to rank 0 over RCCL
         del wl

@@ -34,7 +34,8 @@ for cb in "C2 1024 1024" "C3 256 1024" "C4 256 4096" "C5 8 469"; do
   python3 tools/pmc_summary.py gpurun_out/pmc_${TAG}_$1 $1 $2 $3 $TAG > gpurun_out/traffic_${1,,}_b$2.json || exit 1
   cp gpurun_out/traffic_${1,,}_b$2.json profiles/
 done
-timeout -k 10 900 python bench.py --out gpurun_out/${TAG}_bench.json > gpurun_out/${TAG}_bench.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -c 600 gpurun_out/${TAG}_bench.json
+OUT=${OUT:-out}; mkdir -p $OUT
+timeout -k 10 900 python bench.py --full --out $OUT/${TAG}_bench.json > $OUT/${TAG}_bench.log 2>&1
+rc=$?; echo "bench rc=$rc"; tail -c 600 $OUT/${TAG}_bench.json
 [ $rc -eq 0 ] || exit $rc
 echo "final session done"

@@ -17,14 +17,14 @@ if [[ $STEPS == *tests* ]]; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then stop pytest $rc; fi
 fi
 if [[ $STEPS == *bench* ]]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:-} --out "$OUT/bench_$TAG.json" > "$OUT/bench_$TAG.log" 2>&1
+  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:---full} --out "$OUT/bench_$TAG.json" > "$OUT/bench_$TAG.log" 2>&1
   rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench_$TAG.log"
   [ $rc -eq 0 ] || stop bench $rc
 fi
 if [[ $STEPS == *prof* ]]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 ${PROF_TIMEOUT:-600} rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG" -o run --output-format csv -- \
-      python3 "$ROOT/bench.py" ${PROF_ARGS:---steps 5 --warmup 1 --no-cpu-baseline --no-pcie --no-index --no-reader} > "$OUT/prof_$TAG.log" 2>&1
+      python3 "$ROOT/bench.py" ${PROF_ARGS:---full --steps 5 --warmup 1 --no-cpu-baseline --no-pcie --no-index --no-reader} > "$OUT/prof_$TAG.log" 2>&1
   rc=$?; echo "rocprof rc=$rc"; tail -3 "$OUT/prof_$TAG.log"
   [ $rc -eq 0 ] || stop rocprof $rc
 fi
