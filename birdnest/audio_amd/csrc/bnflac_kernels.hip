@@ -47,7 +47,9 @@ __constant__ uint16_t g_crc16_tab[8][256]; /* slice-by-8 */
 __constant__ uint16_t g_crc16_xpow[40];    /* x^(8*2^j) mod P for j < 40 */
 /* Debug event counters (wave-level events, enabled by ablate bit 0x100; timing runs
  * leave them off).  0 fused chunks, 1 generic chunks, 2 DMA landing waits, 3 slow Rice
- * codewords, 4 refills, 5 waves. */
+ * codewords, 4 refills, 5 waves, 6 k_decode_st tails that continued the running CRC-16 (lanes),
+ * 7 of those, the ones whose remainder differs from the re-read's (-DBNFLAC_CRC_FOLD_CHECK
+ * builds only, with or without 0x100). */
 __device__ unsigned long long g_stats[16]; /* 8.. : s_memtime cycles per phase, summed over waves */
 /* Phase timers (s_memtime) for the debug counters; compiled in only with
  * -DBNFLAC_PHASE_TIMERS, because a scalar-memory op anywhere in the loop makes hipcc's
@@ -121,6 +123,9 @@ DEV void gst128(uint64_t addr, u32x4 v) { *(__attribute__((address_space(1))) u3
 #define BNF_MODE_NOST 0x40000u
 #define BNF_MODE_STREDO 0x80000u
 #define BNF_ABLATE_NO_W8SPLIT 0x100000u /* host A/B bit: the W = 8 instance as one launch */
+/* A/B bit (exact): k_decode_st keeps no running CRC-16 of channel 1 in its chunk loop; the tail
+ * reads channel 1 again from k_parse's prefix on */
+#define BNF_ABLATE_NO_STFOLD 0x40u
 
 /* ----------------------------------------------------------------- bit reader */
 #define RING_MAX 16       /* 16-byte slots per lane (k_parse and k_decode_st use 8) */
@@ -927,7 +932,7 @@ DEV void crcz_line(CrcZ &c, uint4 (&v)[4], uint32_t h) {
  * already holds the lines [b0 & ~63, from) (from: a line boundary) */
 template <int NL = CRC_LINES>
 DEV bool st_crc16_ok(const uint8_t *__restrict__ bytes, uint64_t b0, uint64_t b1, CrcZ c = CrcZ{0u, 0u, 0u},
-                     uint64_t from = 0) {
+                     uint64_t from = 0, CrcZ *fin = nullptr) { /* fin: the final remainder (check builds) */
     const uint64_t p0 = max(b0 & ~(uint64_t)63u, from);
     const uint32_t h = p0 < b0 ? (uint32_t)(b0 & 63u) : 0u;
     const uint32_t nl = b1 > p0 ? (uint32_t)((b1 - p0) >> 6) : 0u;
@@ -980,6 +985,7 @@ DEV bool st_crc16_ok(const uint8_t *__restrict__ bytes, uint64_t b0, uint64_t b1
             crcz_blk(c, v);
         }
     }
+    if (fin) *fin = c;
     return crcz_zero(c);
 }
 /* The CRC-16 hand-off to the decode tails, 8 words per frame (crcp[8f..8f+7]): r0, r1 |
@@ -3224,10 +3230,24 @@ struct StCh {
     uint32_t q[8];  /* history: q[m & 7] = s_m | s_(m-1) << 16 (16-bit halves) */
     int32_t sh;         /* effective shift of the libFLAC path */
     uint32_t k, km, k1, k32; /* Rice parameter, 31 - k, k + 1, 32 - k */
-    uint32_t esc, left, pidx, nparts, psamples, plen, pesc, porder, order;
-    uint32_t wasted;
-    int32_t lim, mx, mn; /* operand range of the path, sample range seen */
+    uint32_t left;
+    /* the state read only at partition switches, in the generic steps and in the tail, in one
+     * word (the fused loop carries it across every chunk): partition index (bits 0-15, at most
+     * 2^15), partition order (16-19), predictor order (20-23, at most 8 here), 5-bit Rice
+     * parameters (24), wasted bits (25-29), the partition is escaped (30).  The partition
+     * length follows from the blocksize. */
+    uint32_t pw;
+    int32_t mx, mn; /* sample range seen (the path's operands are int16: ST_LIM) */
+    DEV uint32_t pidx() const { return pw & 0xFFFFu; }
+    DEV uint32_t porder() const { return (pw >> 16) & 15u; }
+    DEV uint32_t order() const { return (pw >> 20) & 15u; }
+    DEV uint32_t plen() const { return 4u + ((pw >> 24) & 1u); }
+    DEV uint32_t pesc() const { return (pw & (1u << 24)) ? 31u : 15u; }
+    DEV uint32_t wasted() const { return (pw >> 25) & 31u; }
+    DEV bool esc() const { return (pw & (1u << 30)) != 0u; }
+    DEV bool parts_left() const { return pidx() < (1u << porder()); }
 };
+#define ST_LIM 0x7FFF
 
 /* lo | hi << 16 from the low halves */
 DEV uint32_t st_pk(int32_t lo, int32_t hi) { return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u); }
@@ -3262,7 +3282,6 @@ DEV bool st_setup(StCh &z, uint32_t bps, uint32_t bs, uint64_t limit) {
     }
     if (!in16) return false;
     z.sh = 0;
-    z.lim = 0x7FFF;
     if (h.type == T_LPC) {
 #pragma unroll
         for (int t = 0; t < 8; t++) c[t] = ((uint32_t)t < h.order) ? coef[t] : 0;
@@ -3279,16 +3298,8 @@ DEV bool st_setup(StCh &z, uint32_t bps, uint32_t bs, uint64_t limit) {
     for (int k = 0; k < 4; k++) z.cp[k] = st_pk(c[2 * k], c[2 * k + 1]);
 #pragma unroll
     for (int t = 0; t < 8; t++) z.q[t] = st_pk(w[t], t ? w[t - 1] : 0);
-    z.order = h.order;
-    z.wasted = h.wasted;
-    z.porder = h.porder;
-    z.nparts = 1u << h.porder;
-    z.psamples = h.porder ? bs >> h.porder : bs - h.order;
-    z.plen = h.rice2 ? 5u : 4u;
-    z.pesc = h.rice2 ? 31u : 15u;
+    z.pw = ((h.porder & 15u) << 16) | ((h.order & 15u) << 20) | ((h.rice2 ? 1u : 0u) << 24) | ((h.wasted & 31u) << 25);
     z.left = 0;
-    z.pidx = 0;
-    z.esc = 0;
     z.k = 0;
     z.km = 31;
     z.k1 = 1;
@@ -3373,6 +3384,35 @@ DEV int32_t st_next(Z &z, uint64_t limit, uint32_t &trunc, uint32_t nst) {
     }
     z.left--;
     if (z.esc) return br_read_s(z.b, z.k);
+    return st_rice(z, limit, trunc, nst);
+}
+/* the two above for k_decode_st's packed state (StCh::pw; bs: the frame's blocksize) */
+DEV void st_partition(StCh &z, uint32_t bs) {
+    const uint32_t kk = br_read(z.b, z.plen());
+    const uint32_t po = z.porder(), ps = po ? bs >> po : bs - z.order();
+    z.left = (po == 0 || z.pidx() > 0) ? ps : ps - z.order();
+    if (kk < z.pesc()) {
+        z.k = kk;
+        z.pw &= ~(1u << 30);
+    } else {
+        z.k = br_read(z.b, 5);
+        z.pw |= 1u << 30;
+    }
+    z.km = 31u - z.k;
+    z.k1 = z.k + 1u;
+    z.k32 = 32u - z.k;
+    z.pw++; /* the partition index: at most 2^15, no carry out of its field */
+}
+DEV int32_t st_next(StCh &z, uint32_t bs, uint64_t limit, uint32_t &trunc, uint32_t nst) {
+    while (z.left == 0) {
+        if (!z.parts_left()) {
+            trunc = 1;
+            return 0;
+        }
+        st_partition(z, bs);
+    }
+    z.left--;
+    if (z.esc()) return br_read_s(z.b, z.k);
     return st_rice(z, limit, trunc, nst);
 }
 
@@ -3556,6 +3596,111 @@ DEV uint32_t st_refill_issue(BR &b, bool want) { /* returns a lower bound of the
     return nd;
 }
 
+/* k_decode_st's running CRC-16 of channel 1.  Every byte of channel 1 passes through its
+ * ring, so the frame's remainder (the tail's T^4 form, continuing k_parse's prefix of the
+ * lines before channel 1) is kept running in the chunk loop and the tail reads only the last
+ * lines again.  c holds the lines before line fl (absolute 64-byte line index; ~0u: no
+ * running remainder for this lane), whatever happens to the ring: a line is folded only while
+ * the ring holds it, so a lane whose ring moved on without it (a blocking refill of the rare
+ * paths) simply stops folding, and its tail reads on from line fl as it did from the prefix. */
+struct StFold {
+    CrcZ c;
+    uint32_t fl;
+};
+/* A refill point of the chunk loop (whole wave; every DMA issued has landed, and this
+ * channel's next ones are not issued yet).  The ring holds the lines [iend / 4 - 2, iend / 4);
+ * lines and the ring's groups are both 64-byte units counted from `words`.  Lanes retire
+ * their groups at different refill points, so a fold at the point of retirement runs for
+ * the whole wave at nearly every point (two a chunk, ~100 VALU each) for the one lane in
+ * five that needs it.  So the lanes fold together, once a chunk:
+ * - end of chunk (end): every line up to the cursor's group (the line of word wi), that
+ *   line included when `ahead`: the bits still to come in channel 1 cannot end inside it
+ *   (k_decode_st's bound from the partition's Rice parameter).  The mid-chunk refill of the
+ *   next chunk then retires a line already folded;
+ * - mid chunk (!end): only a lane whose refill is about to retire the line it has not
+ *   folded (no `ahead` at the chunk's start: partition ends, the frame's last chunks).
+ * Only a lane that decodes on (want) folds.  Word wi is two words ahead of the cursor, so the
+ * cursor may still be in the line before its group: a frame whose last samples and footer
+ * fit those 64 bits ends inside a folded line, and st_crc16_run's bound catches it. */
+DEV void st_fold_point(StFold &r, const BR &b, uint32_t lane, bool want, bool end, bool ahead) {
+    const uint32_t cl = b.wi >> 4, il = b.iend >> 2;
+    const uint32_t lim = cl + ((end && ahead) ? 1u : 0u);
+#pragma unroll 1
+    for (;;) { /* at most the ring's two lines */
+        const bool go = want && r.fl < lim && r.fl < il && (end ? r.fl + 2u >= il : (r.fl + 2u == il && il == cl + 1u));
+        if (!any_lane(go)) break;
+        if (go) {
+            const lds_u32x4 *p = (const lds_u32x4 *)(b.ring + (r.fl & 1u) * (4u * RING_LANE_DW) + lane * 4u);
+            /* two 16-byte pieces in flight (8 VGPRs, not the line's 16); the waits name the
+             * pieces, so the arithmetic on them stays behind */
+            u32x4 a = lds_ld128(p), c = lds_ld128(p + RING_LANE_DW / 4u);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(c)::"memory");
+            crcz_blk(r.c, make_uint4(a.x, a.y, a.z, a.w));
+            a = lds_ld128(p + 2u * (RING_LANE_DW / 4u));
+            crcz_blk(r.c, make_uint4(c.x, c.y, c.z, c.w));
+            c = lds_ld128(p + 3u * (RING_LANE_DW / 4u));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(c)::"memory");
+            crcz_blk(r.c, make_uint4(a.x, a.y, a.z, a.w));
+            crcz_blk(r.c, make_uint4(c.x, c.y, c.z, c.w));
+            r.fl++;
+        }
+    }
+}
+/* Start of the running remainder: k_parse's hand-off record, when it is this frame's.  The
+ * prefix ends at channel 1's line or, when the reader's two-word lookahead had crossed into
+ * the next line, one before the ring's first line: that line is read here (once per frame). */
+DEV void st_fold_start(StFold &r, const BR &b, const uint32_t *__restrict__ words, const uint32_t *__restrict__ crcp,
+                       uint32_t f, uint64_t frame_off, bool on) {
+    r.c = CrcZ{0u, 0u, 0u};
+    r.fl = ~0u;
+    if (on) {
+        const u32x4 q = *(const u32x4 *)(crcp + CRCP_WORDS * (uint64_t)f);
+        if (q.z && q.w == (uint32_t)frame_off) {
+            r.c = CrcZ{q.x, q.y & 0x0FFFFFFFu, q.y >> 31};
+            r.fl = (uint32_t)(frame_off >> 6) + q.z - 1u;
+        }
+    }
+    const bool behind = r.fl != ~0u && r.fl + 3u == (b.iend >> 2);
+    if (any_lane(behind)) {
+        if (behind) {
+            const uint4 *g = (const uint4 *)((const uint8_t *)words + (uint64_t)r.fl * 64u);
+            uint4 v[4];
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) v[i] = g[i];
+            crcz_line(r.c, v, 0u);
+            r.fl++;
+        }
+    }
+}
+/* The tail's verdict of the frame [b0, b1): the hand-off's verdict as st_crc16_frame, else the
+ * running remainder continued from line r.fl (not past b1: a frame that ends inside a folded
+ * line has bytes behind its footer in the remainder), else st_crc16_frame's prefix or whole
+ * frame.  used: the running remainder was continued; fin: the final remainder. */
+DEV bool st_crc16_run(const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ crcp, uint32_t f, uint64_t b0,
+                      uint64_t b1, const StFold &r, bool &used, CrcZ *fin = nullptr) {
+    CrcZ c = CrcZ{0u, 0u, 0u};
+    uint64_t from = 0;
+    used = false;
+    if (crcp) {
+        const u32x4 v = *(const u32x4 *)(crcp + CRCP_WORDS * (uint64_t)f + 4u);
+        if (v.x && v.z == (uint32_t)b0 && b0 + v.x == b1) return v.y != 0u;
+    }
+    const uint64_t rf = (uint64_t)r.fl * 64u;
+    if (r.fl != ~0u && rf <= b1 && rf > b0) {
+        c = r.c;
+        from = rf;
+        used = true;
+    } else if (crcp) {
+        const u32x4 q = *(const u32x4 *)(crcp + CRCP_WORDS * (uint64_t)f);
+        const uint64_t pf = ((b0 >> 6) + q.z - 1u) * 64u;
+        if (q.z && q.w == (uint32_t)b0 && pf <= b1) {
+            c = CrcZ{q.x, q.y & 0x0FFFFFFFu, q.y >> 31};
+            from = pf;
+        }
+    }
+    return st_crc16_ok(bytes, b0, b1, c, from, fin);
+}
+
 
 /* Fused-path cursor (4-slot ring).  ra is the LDS byte offset of ring word wi inside the
  * channel's ring: bits 2-3 word in block, 4-9 lane, 10-11 slot.  Moving it one word on is
@@ -3666,8 +3811,8 @@ DEV void st_lpc_out(StCh &z0, StCh &z1, uint32_t u0, uint32_t u1, int32_t (&L)[4
         if (AS < 0 && __builtin_expect(anyw, 0)) { /* wasted bits (wave-uniform test; AS >= 0: none) */
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                L[q] = (int32_t)((uint32_t)L[q] << z0.wasted);
-                R[q] = (int32_t)((uint32_t)R[q] << z1.wasted);
+                L[q] = (int32_t)((uint32_t)L[q] << z0.wasted());
+                R[q] = (int32_t)((uint32_t)R[q] << z1.wasted());
             }
         }
         if (STG && AS >= 0) { /* no wasted bits: the history pairs hold the samples */
@@ -3774,17 +3919,17 @@ DEV bool st_gen_step(StCh &z0, StCh &z1, int32_t (&L)[4], int32_t (&R)[4], uint6
     if (v) {
         int32_t p0, p1;
         st_dot2<T>(z0, z1, p0, p1);
-        if (n < z0.order) s0 = (int32_t)(int16_t)z0.q[T];
-        else s0 = (int32_t)((uint32_t)st_next(z0, limit, trunc, nst) + (uint32_t)(p0 >> z0.sh));
-        if (n < z1.order) s1 = (int32_t)(int16_t)z1.q[T];
-        else s1 = (int32_t)((uint32_t)st_next(z1, limit, trunc, nst) + (uint32_t)(p1 >> z1.sh));
+        if (n < z0.order()) s0 = (int32_t)(int16_t)z0.q[T];
+        else s0 = (int32_t)((uint32_t)st_next(z0, bs, limit, trunc, nst) + (uint32_t)(p0 >> z0.sh));
+        if (n < z1.order()) s1 = (int32_t)(int16_t)z1.q[T];
+        else s1 = (int32_t)((uint32_t)st_next(z1, bs, limit, trunc, nst) + (uint32_t)(p1 >> z1.sh));
         st_range(z0, s0, s0);
         st_range(z1, s1, s1);
         z0.q[T] = __builtin_amdgcn_perm(z0.q[(T + 7) & 7], (uint32_t)s0, 0x05040100u);
         z1.q[T] = __builtin_amdgcn_perm(z1.q[(T + 7) & 7], (uint32_t)s1, 0x05040100u);
     }
-    L[T & 3] = (int32_t)((uint32_t)s0 << z0.wasted);
-    R[T & 3] = (int32_t)((uint32_t)s1 << z1.wasted);
+    L[T & 3] = (int32_t)((uint32_t)s0 << z0.wasted());
+    R[T & 3] = (int32_t)((uint32_t)s1 << z1.wasted());
     bool stored = false;
     if ((T & 3) == 3) {
         const uint32_t nq = n - 3u;
@@ -3850,7 +3995,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         ok = st_setup(z1, sub_bps(fi, 1), bs, limit);
     }
     const uint32_t as = ok ? fi.assignment : 0u;
-    const bool anyw = any_lane(ok && (z0.wasted | z1.wasted) != 0u);
+    const bool anyw = any_lane(ok && (z0.wasted() | z1.wasted()) != 0u);
     const uint32_t as_u = __builtin_amdgcn_readfirstlane(as);
     const bool as_uni = !any_lane(ok && as != as_u);
     /* the fused chunks' compile-time assignment: one per wave, no wasted bits */
@@ -3864,6 +4009,11 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
     for (int o = 32; o > 0; o >>= 1) mybs = max(mybs, (uint32_t)__shfl_xor(mybs, o));
     const uint32_t nchunks = (mybs + ST2_CHK - 1) / ST2_CHK;
     uint32_t trunc = 0;
+    /* channel 1's running CRC-16 (StFold), folded at the chunk's refill points (st_fold_point);
+     * the wave-uniform switch BNF_ABLATE_NO_STFOLD leaves the tail its re-read from the prefix */
+    const bool fold_on = crcp != nullptr && !(ablate & (BNF_ABLATE_NO_STFOLD | 1u));
+    StFold fold;
+    st_fold_start(fold, z1.b, words, crcp, f, ok ? fi.frame_off : 0u, fold_on && ok);
     wait_vm(); /* setup loads done: the store count starts from zero */
     uint32_t nst = 0; /* vector-memory ops (PCM stores) issued by this wave since the last refill's DMAs */
     const bool sto = !(ablate & 2u);
@@ -3871,11 +4021,12 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
      * issue the next blocks; stores issued after it are younger.  (Round 5: waiting for the
      * refill before last instead, with the landing check covering the newest group, measured
      * 32% slower on C2: a lane entering its newest group stalls the whole wave.) */
-    auto refill = [&](bool want) {
+    auto refill = [&](bool want, bool end = false, bool ahead = false) {
         wait_vm_n(nst);
         z0.b.vendw = z0.b.iend * 4u;
         z1.b.vendw = z1.b.iend * 4u;
         st_refill_issue(z0.b, want);
+        if (fold_on) st_fold_point(fold, z1.b, lane, want, end, ahead); /* before the DMAs that overwrite the line */
         st_refill_issue(z1.b, want);
         nst = 0;
     };
@@ -3886,9 +4037,9 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         const bool valid = ok && n0 < bs;
         bool fast = valid && n0 >= 8u && n0 + ST2_CHK <= bs && !(ablate & 12u);
         if (fast) { /* partition headers at the chunk boundary (aligned partitions) */
-            if (z0.left == 0 && z0.pidx < z0.nparts) st_partition(z0);
-            if (z1.left == 0 && z1.pidx < z1.nparts) st_partition(z1);
-            fast = !z0.esc && !z1.esc && z0.left >= ST2_CHK && z1.left >= ST2_CHK;
+            if (z0.left == 0 && z0.parts_left()) st_partition(z0, bs);
+            if (z1.left == 0 && z1.parts_left()) st_partition(z1, bs);
+            fast = !z0.esc() && !z1.esc() && z0.left >= ST2_CHK && z1.left >= ST2_CHK;
         }
         const bool fused = !any_lane(valid && !fast);
         u32x4 pk[4], pk0[4]; /* STG: the chunk's eight 16-byte units of this lane's frame run (128 bytes): pk0 from the first half, pk from the second */
@@ -3962,7 +4113,11 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         }
         const uint64_t tb = tnow(tmon);
         tm_dec += tb - ta;
-        refill(valid && n0 + ST2_CHK < bs);
+        /* the fold may take the cursor's own line when channel 1 has more than that line's
+         * bits (and the two-word lookahead's) still to come: the rest of the partition at k + 1
+         * bits a sample or more, every later sample at one or more */
+        const uint32_t rest = bs - min(bs, n0 + ST2_CHK), inp = z1.esc() ? 0u : min(rest, z1.left);
+        refill(valid && n0 + ST2_CHK < bs, true, inp * z1.k1 + (rest - inp) >= 576u);
         const uint64_t tc = tnow(tmon);
         tm_ref += tc - tb;
         if (STG && fused) {
@@ -4013,14 +4168,14 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
     uint32_t crc_read = 0;
     uint64_t end_byte = 0, resume = 0;
     if (ok) {
-        if (z0.mx > z0.lim || z0.mn < -z0.lim - 1 || z1.mx > z1.lim || z1.mn < -z1.lim - 1) ok = false;
+        if (z0.mx > ST_LIM || z0.mn < -ST_LIM - 1 || z1.mx > ST_LIM || z1.mn < -ST_LIM - 1) ok = false;
         if (trunc) ok = false;
     }
     if (ok) {
-        while (z1.pidx < z1.nparts) { /* finish_partitions */
-            const uint32_t kk = br_read(z1.b, z1.plen);
-            if (kk >= z1.pesc) br_read(z1.b, 5);
-            z1.pidx++;
+        while (z1.parts_left()) { /* finish_partitions */
+            const uint32_t kk = br_read(z1.b, z1.plen());
+            if (kk >= z1.pesc()) br_read(z1.b, 5);
+            z1.pw++;
         }
         const uint32_t padbits = (uint32_t)((8u - (br_pos(z1.b) & 7u)) & 7u);
         const uint32_t zp = br_read(z1.b, padbits);
@@ -4030,16 +4185,41 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         if (br_pos(z1.b) > limit) ok = false;
         resume = br_pos(z1.b);
     }
+    /* the record's flags and offset are read again here, not carried through the chunk loop
+     * (nothing writes a stereo frame's record while this kernel runs) */
+    const uint32_t fl_flags = mine ? info[f].flags : 0u;
+    const uint64_t frame_off = ok ? info[f].frame_off : 0u;
     /* CRC-16 of the frame bytes (read_frame_'s footer check @0x10011a01), by the table-free
      * zero test over frame + footer (st_crc16_ok; round 6: 10.8 -> 10.5 ms on C2 against round
      * 5's 11-bit LDS tables, same box), continuing k_parse's prefix of the lines before channel
-     * 1 when the batch has one (st_crc16_frame: 10.7 -> 9.6 ms).  The tail is bound by the
-     * re-read: every wave of a CU reaches it together, so those bytes go at the HBM rate with no
-     * decode beside them (no CRC at all: ~8.6 ms).  Keeping the remainder running inside the
-     * chunk loop instead needs live VGPRs the loop does not have at 256: it spilled (11-89
-     * VGPRs in two attempts) and ran 30% slower with the fold off. */
+     * 1 when the batch has one (10.7 -> 9.6 ms).  A tail that reads channel 1 again is bound
+     * by that re-read: every wave of a CU reaches it together, so those bytes go at the HBM rate
+     * with no decode beside them (no CRC at all: ~8.6 ms).  So the chunk loop keeps the
+     * remainder running over channel 1's ring groups (StFold; four VGPRs, which the loop has
+     * since StCh's cold state shares one word: round 6's attempts spilled 11-89 VGPRs at 256),
+     * and st_crc16_run continues it over the frame's last lines only, or, for a lane whose
+     * fold stopped early, from wherever it stopped. */
     uint32_t crc = crc_read;
-    if (ok && !(ablate & 1u) && !st_crc16_frame((const uint8_t *)words, crcp, f, fi.frame_off, end_byte + 2u)) ok = false;
+    if (ok && !(ablate & 1u)) {
+        bool used;
+#ifdef BNFLAC_CRC_FOLD_CHECK
+        /* check build: both verdicts, and the lanes whose two final remainders differ */
+        CrcZ ra = CrcZ{0u, 0u, 0u}, rb = CrcZ{0u, 0u, 0u};
+        StFold none;
+        none.c = CrcZ{0u, 0u, 0u};
+        none.fl = ~0u;
+        bool unused;
+        const bool va = st_crc16_run((const uint8_t *)words, crcp, f, frame_off, end_byte + 2u, fold, used, &ra);
+        const bool vb = st_crc16_run((const uint8_t *)words, crcp, f, frame_off, end_byte + 2u, none, unused, &rb);
+        const bool differ = used && (va != vb || ra.r0 != rb.r0 || ((ra.r1 ^ rb.r1) & 0x0FFFFFFFu) != 0u ||
+                                     (__builtin_popcount(ra.px ^ rb.px) & 1) != 0);
+        if (differ) atomicAdd(&g_stats[7], 1ull);
+        if (!va) ok = false;
+#else
+        if (!st_crc16_run((const uint8_t *)words, crcp, f, frame_off, end_byte + 2u, fold, used)) ok = false;
+#endif
+        if (z0.b.stats && used) atomicAdd(&g_stats[6], 1ull); /* lanes (not waves): tails that continued the running remainder */
+    }
     if (ok && crc != crc_read) ok = false;
     if (ok) {
         info[f].resume_bit = resume;
@@ -4047,7 +4227,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         info[f].crc16_calc = crc;
         info[f].crc_ok = 1u;
     } else if (mine) {
-        info[f].flags = fi.flags | BNF_FL_REDO;
+        info[f].flags = fl_flags | BNF_FL_REDO;
     }
     if (tmon && lane == 0) {
         const uint64_t t_end = tnow(tmon);

@@ -137,6 +137,15 @@ static int ensure_device(int dev) {
  * bit4 k_parse subframe walk.  0x2000 is an exact A/B switch: the 24-bit FLACFileReader
  * wide flush (pack_wide24) off. */
 extern "C" BNFLAC_API void bnflac_debug_set_ablate(uint32_t flags) { bnf_set_ablate(flags); }
+/* 1 in a -DBNFLAC_CRC_FOLD_CHECK build (k_decode_st's tail computes the CRC-16 both ways and
+ * counts the lanes that disagree, bnflac_debug_stats slot 7); 0 in the shipped library */
+extern "C" BNFLAC_API int bnflac_debug_crc_fold_check(void) {
+#ifdef BNFLAC_CRC_FOLD_CHECK
+    return 1;
+#else
+    return 0;
+#endif
+}
 extern "C" void bnf_set_parse_wave(int mode);
 /* parse kernel: -1 auto (k_parse_wave for small launches), 0 k_parse, 1 k_parse_wave (tests, A/B) */
 extern "C" BNFLAC_API void bnflac_debug_set_parse_wave(int mode) { bnf_set_parse_wave(mode); }

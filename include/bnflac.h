@@ -184,8 +184,15 @@ BNFLAC_API int bnflac_decode_parsed(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
  * bit2 restore, bit3 Rice decode, bit4 subframe walk).  Output is wrong while set.
  * Exception: bit 0x800 only routes every k_decode chunk through the generic path (exact).
  * Bit 0x10000000 aims k_decode_st's / k_decode_sw's PCM stores at a 513 KB window at the
- * start of d_out (an L2-resident footprint); it is ignored when out_bytes < 1 MiB. */
+ * start of d_out (an L2-resident footprint); it is ignored when out_bytes < 1 MiB.
+ * Bit 0x40 is an exact A/B switch (identical PCM and records): k_decode_st keeps no running
+ * CRC-16 of channel 1 in its chunk loop, and its tail reads channel 1 again from k_parse's
+ * prefix on, as it did before the running remainder. */
 BNFLAC_API void bnflac_debug_set_ablate(uint32_t flags);
+/* Debug: 1 when the library was built with -DBNFLAC_CRC_FOLD_CHECK (never the shipped one):
+ * k_decode_st's tail then computes the frame's CRC-16 both from the running remainder and from
+ * the re-read, and bnflac_debug_stats slot 7 counts the lanes whose remainders differ. */
+BNFLAC_API int bnflac_debug_crc_fold_check(void);
 /* Development / test switch: parse kernel (-1 auto, 0 lane-per-frame k_parse, 1 wave-per-frame
  * k_parse_wave); both write identical records. */
 BNFLAC_API void bnflac_debug_set_parse_wave(int mode);
@@ -213,7 +220,8 @@ BNFLAC_API uint64_t bnflac_debug_decode_seg_launches(void);
 BNFLAC_API int bnflac_debug_parse_wave_stats(uint64_t *out8, int reset);
 /* Debug: k_decode event counters collected while ablate bit 0x100 is set: [0..5] fused
  * chunks, generic chunks, DMA landing waits, slow Rice codewords, refills, waves (wave-level
- * events); [8..12] shader-clock cycles summed over waves in setup, chunk decode, refill,
+ * events); [6] k_decode_st frames whose tail continued the running CRC-16 of channel 1; [7]
+ * see bnflac_debug_crc_fold_check; [8..12] shader-clock cycles summed over waves in setup, chunk decode, refill,
  * pack, tail.  out16 holds 16 values.  Synchronous; reset != 0 clears them. */
 BNFLAC_API int bnflac_debug_stats(uint64_t *out16, int reset);
 
