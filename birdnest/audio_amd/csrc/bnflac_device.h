@@ -67,6 +67,32 @@ typedef struct {
     uint64_t total_samples;
 } bnf_stream_params;
 
+/* One stream of a bnflac_index_streams batch (== bnflac_stream_desc). */
+typedef struct {
+    uint64_t begin, end;    /* the stream's bytes */
+    uint64_t first_offset;  /* absolute offset of the byte after the metadata blocks */
+    uint64_t total_samples; /* 0: unknown (no EOS rule) */
+} bnf_stream_desc;
+
+/* Device scratch of the batched frame chain (bnf_launch_chain_streams); C = cand_cap,
+ * S = nstreams, B = scan workgroups of the buffer (bnf_scan_blocks). */
+typedef struct {
+    uint32_t *ctl;           /* 4 words */
+    uint32_t *blk;           /* B + 1 */
+    uint32_t *csum;          /* max(B, C, S) / 1024 + 2 */
+    uint64_t *asum;          /* the same */
+    uint64_t *cand;          /* C */
+    bnf_frame_info *info;    /* C */
+    int32_t *seg;            /* C */
+    uint32_t *key, *mark;    /* C each */
+    uint32_t *pos;           /* C + 1 */
+    uint64_t *bs, *smp;      /* C and C + 1 */
+    int32_t *jump;           /* 2 C */
+    uint32_t *clo, *chi, *kept; /* S each */
+    int32_t *head;           /* S */
+    uint64_t *ssum, *ss;     /* S and S + 1 */
+} bnf_ms_scratch;
+
 /* How k_decode positions frames in the output buffer. */
 enum {
     BNF_POS_BY_NUMBER = 0,   /* out_sample = header sample number - base (libFLAC's own positioning) */

@@ -3199,6 +3199,430 @@ __global__ void __launch_bounds__(256) k_chain_emit(const uint64_t *__restrict__
         d_info[p] = fi;
     }
 }
+
+/* =================================================== batched frame chain (bnflac_index_streams)
+ * The chain above for many streams in one buffer, with no count on the host: every kernel is
+ * launched on a grid sized by the candidate capacity and reads the candidate count from
+ * ctl[MS_N] (0 when the capacity overflowed or the descriptor table is bad, so that nothing
+ * past the scratch is touched).  Sync candidates are taken over the whole buffer; candidate p
+ * belongs to stream s iff begin[s] <= p and p + 2 <= end[s] (the single-stream scan's
+ * p + 1 < n), the others -- in the gaps, or straddling an end -- belong to none and are never
+ * valid.  The streams ascend, so a stream's candidates are the index range [clo[s], chi[s]).
+ * The keys R(c) are taken over the whole buffer (the equality test does not care where the
+ * pair lies); successors are looked for inside the stream's range only, so chains never
+ * cross streams and one pointer doubling covers all of them.
+ * The stream end as the truncation limit: parse_frame bounds its walk by the buffer, not by
+ * end[s].  Its cursor only moves forward and stops at frame_off * 8 + sub_start[C - 1], so
+ * "OK with the stream's own end as the limit" is "OK under the buffer's limit, and that last
+ * position <= end[s] * 8": an error met at or before end[s] is met on the same bytes in both,
+ * and whatever happens past end[s] is TRUNC or ERROR for the stream alone.  The filter is
+ * applied where KEY_OK is set (k_ms_keys_apply).
+ * All prefix sums are three launches (block sums, their scan, apply): launch boundaries are
+ * the only ordering between workgroups.  The running sample count is taken over the
+ * candidates (0 for the unmarked) and rebased at the stream's first candidate, which is the
+ * scan restarted at the stream's first kept frame. */
+enum { MS_BAD = 0, MS_NCAND = 1, MS_N = 2, MS_CTL_WORDS = 4 }; /* ctl: bad table, candidates found, candidates used */
+#define MS_SCAN 1024u /* elements per workgroup of the three-launch scans */
+
+DEV uint32_t ms_n(const uint32_t *__restrict__ ctl) { return ctl[MS_N]; }
+
+/* bit 2 of the status: begin <= first_offset <= end <= nbytes, and begin >= the previous end */
+__global__ void __launch_bounds__(256) k_ms_check(const bnf_stream_desc *__restrict__ sd, uint32_t nstreams,
+                                                  uint64_t nbytes, uint32_t *__restrict__ ctl) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= nstreams) return;
+    const bnf_stream_desc d = sd[s];
+    bool bad = d.begin > d.end || d.end > nbytes || d.first_offset < d.begin || d.first_offset > d.end;
+    if (s > 0 && d.begin < sd[s - 1].end) bad = true;
+    if (bad) atomicOr(&ctl[MS_BAD], 1u);
+}
+
+/* The sync scan on 16-byte words: a thread takes one word and the first byte of the next
+ * (its neighbour's, by a shuffle).  WRITE 0 counts per workgroup (4,096 bytes), 1 writes the
+ * positions from the scanned workgroup offsets. */
+template <int WRITE>
+__global__ void __launch_bounds__(256) k_ms_sync(const uint8_t *__restrict__ d, uint64_t n, uint32_t *__restrict__ blk,
+                                                 uint64_t *__restrict__ out, uint32_t cap) {
+    __shared__ uint32_t wtot[4];
+    const uint64_t base = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u;
+    const uint32_t lane = threadIdx.x & 63u;
+    u32x4 v = u32x4{0u, 0u, 0u, 0u};
+    if (base < n) v = *(const u32x4 *)(d + base); /* the allocation covers whole 16-byte blocks */
+    uint32_t nxt = (uint32_t)__shfl_down((int)v.x, 1) & 0xFFu;
+    if (lane == 63u) nxt = base + 16u < n ? d[base + 16u] : 0u;
+    const uint32_t w[5] = {v.x, v.y, v.z, v.w, nxt};
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) {
+        const uint32_t b0 = (w[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
+        const uint32_t b1 = (w[(k + 1u) >> 2] >> (8u * ((k + 1u) & 3u))) & 0xFFu;
+        if (b0 == 0xFFu && (b1 >> 2) == 0x3Eu && base + k + 1u < n) m |= 1u << k;
+    }
+    const uint32_t c = (uint32_t)__builtin_popcount(m);
+    uint32_t incl = c;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o);
+        if (lane >= (unsigned)o) incl += y;
+    }
+    if (lane == 63u) wtot[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    if (!WRITE) {
+        if (threadIdx.x == 0) blk[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        return;
+    }
+    uint32_t pos = blk[blockIdx.x] + incl - c;
+    for (uint32_t wv = 0; wv < (threadIdx.x >> 6); wv++) pos += wtot[wv];
+    while (m) {
+        const uint32_t k = (uint32_t)__builtin_ctz(m);
+        m &= m - 1u;
+        if (pos < cap) out[pos] = base + k;
+        pos++;
+    }
+}
+
+/* the candidate count: found (the status' word 1) and used */
+__global__ void k_ms_set_n(const uint32_t *__restrict__ total, uint32_t cap, uint32_t *__restrict__ ctl) {
+    const uint32_t t = *total;
+    ctl[MS_NCAND] = t;
+    ctl[MS_N] = (ctl[MS_BAD] || t > cap) ? 0u : t;
+}
+
+/* ---- three-launch scans.  Exclusive prefix inside a 1,024-thread workgroup; `tot` is the
+ * workgroup's total.  ws: 16 words of LDS per call site. */
+template <class T, bool XOR>
+DEV T ms_block_excl(T x, T *ws, T &tot) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    T incl = x;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(incl, o);
+        if (lane >= (unsigned)o) incl = XOR ? (incl ^ y) : (incl + y);
+    }
+    if (lane == 63u) ws[wv] = incl;
+    __syncthreads();
+    T pre = 0, all = 0;
+    for (uint32_t k = 0; k < 16u; k++) {
+        const T t = ws[k];
+        if (k < wv) pre = XOR ? (pre ^ t) : (pre + t);
+        all = XOR ? (all ^ t) : (all + t);
+    }
+    tot = all;
+    return XOR ? (pre ^ incl ^ x) : (pre + incl - x);
+}
+
+/* the workgroup sums' own exclusive scan, in place (one workgroup) */
+template <class T, bool XOR>
+DEV void ms_scan_sums(T *__restrict__ v, uint32_t nb, T *ws) {
+    __shared__ T carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < nb; base += MS_SCAN) {
+        const uint32_t i = base + threadIdx.x;
+        const T x = i < nb ? v[i] : (T)0;
+        T tot;
+        const T ex = ms_block_excl<T, XOR>(x, ws, tot);
+        const T c = carry;
+        if (i < nb) v[i] = XOR ? (c ^ ex) : (c + ex);
+        __syncthreads();
+        if (threadIdx.x == 0) carry = XOR ? (c ^ tot) : (c + tot);
+        __syncthreads();
+    }
+}
+
+/* element count of a scan: min(*n_ptr, cap) candidates, or cap when the host knows it */
+DEV uint32_t ms_count(const uint32_t *__restrict__ n_ptr, uint32_t cap) { return n_ptr ? min(*n_ptr, cap) : cap; }
+
+/* the keys: XOR scan of the gap words */
+__global__ void __launch_bounds__(MS_SCAN) k_ms_keys_reduce(const uint32_t *__restrict__ gap, const uint32_t *__restrict__ ctl,
+                                                            uint32_t *__restrict__ bsum) {
+    __shared__ uint32_t ws[16];
+    const uint32_t i = blockIdx.x * MS_SCAN + threadIdx.x;
+    uint32_t tot;
+    (void)ms_block_excl<uint32_t, true>(i < ms_n(ctl) ? gap[i] : 0u, ws, tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(MS_SCAN) k_ms_keys_sums(uint32_t *__restrict__ bsum, uint32_t nb) {
+    __shared__ uint32_t ws[16];
+    ms_scan_sums<uint32_t, true>(bsum, nb, ws);
+}
+/* ... in place, with KEY_OK for the candidates that belong to a stream and are valid frame
+ * starts with that stream's end as the limit (see above) */
+__global__ void __launch_bounds__(MS_SCAN) k_ms_keys_apply(uint32_t *__restrict__ gap, const uint32_t *__restrict__ ctl,
+                                                           const uint32_t *__restrict__ bsum,
+                                                           const bnf_frame_info *__restrict__ info,
+                                                           const int32_t *__restrict__ seg,
+                                                           const bnf_stream_desc *__restrict__ sd) {
+    __shared__ uint32_t ws[16];
+    const uint32_t i = blockIdx.x * MS_SCAN + threadIdx.x, n = ms_n(ctl);
+    uint32_t tot;
+    const uint32_t ex = ms_block_excl<uint32_t, true>(i < n ? gap[i] : 0u, ws, tot);
+    if (i >= n) return;
+    uint32_t ok = 0;
+    const int32_t s = seg[i];
+    if (s >= 0 && info[i].status == BNF_ST_OK) {
+        const uint32_t ch = info[i].channels; /* 1..8 for an OK header */
+        const uint64_t last = info[i].frame_off * 8u + info[i].sub_start[(ch - 1u) & 7u];
+        if (last <= sd[s].end * 8u) ok = KEY_OK;
+    }
+    gap[i] = ((bsum[blockIdx.x] ^ ex) & 0xFFFFu) | ok;
+}
+
+/* counts (32-bit) and, with a != nullptr, sums (64-bit) together: exclusive prefixes of
+ * c[0, n) and a[0, n) into co / ao, which have n + 1 entries (the last is the total) */
+__global__ void __launch_bounds__(MS_SCAN) k_ms_add_reduce(const uint32_t *__restrict__ c, const uint64_t *__restrict__ a,
+                                                           const uint32_t *__restrict__ n_ptr, uint32_t cap,
+                                                           uint32_t *__restrict__ csum, uint64_t *__restrict__ asum) {
+    __shared__ uint32_t ws[16];
+    __shared__ uint64_t ws64[16];
+    const uint32_t i = blockIdx.x * MS_SCAN + threadIdx.x, n = ms_count(n_ptr, cap);
+    uint32_t tot;
+    (void)ms_block_excl<uint32_t, false>(i < n ? c[i] : 0u, ws, tot);
+    if (threadIdx.x == 0) csum[blockIdx.x] = tot;
+    if (a) {
+        uint64_t tot64;
+        (void)ms_block_excl<uint64_t, false>(i < n ? a[i] : 0ull, ws64, tot64);
+        if (threadIdx.x == 0) asum[blockIdx.x] = tot64;
+    }
+}
+__global__ void __launch_bounds__(MS_SCAN) k_ms_add_sums(uint32_t *__restrict__ csum, uint64_t *__restrict__ asum, uint32_t nb) {
+    __shared__ uint32_t ws[16];
+    __shared__ uint64_t ws64[16];
+    ms_scan_sums<uint32_t, false>(csum, nb, ws);
+    if (asum) ms_scan_sums<uint64_t, false>(asum, nb, ws64);
+}
+__global__ void __launch_bounds__(MS_SCAN) k_ms_add_apply(const uint32_t *c, const uint64_t *__restrict__ a,
+                                                          const uint32_t *__restrict__ n_ptr, uint32_t cap,
+                                                          const uint32_t *__restrict__ csum, const uint64_t *__restrict__ asum,
+                                                          uint32_t *co /* may be c */, uint64_t *__restrict__ ao) {
+    __shared__ uint32_t ws[16];
+    __shared__ uint64_t ws64[16];
+    const uint32_t i = blockIdx.x * MS_SCAN + threadIdx.x, n = ms_count(n_ptr, cap);
+    uint32_t tot;
+    const uint32_t ex = ms_block_excl<uint32_t, false>(i < n ? c[i] : 0u, ws, tot);
+    if (i <= n) co[i] = csum[blockIdx.x] + ex;
+    if (a) {
+        uint64_t tot64;
+        const uint64_t ex64 = ms_block_excl<uint64_t, false>(i < n ? a[i] : 0ull, ws64, tot64);
+        if (i <= n && ao) ao[i] = asum[blockIdx.x] + ex64;
+    }
+}
+
+/* first index in cand[0, n) whose position is >= x */
+DEV uint32_t ms_lower(const uint64_t *__restrict__ cand, uint32_t n, uint64_t x) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (cand[mid] < x) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
+/* a stream's candidates: positions in [begin, end - 2] */
+__global__ void __launch_bounds__(256) k_ms_ranges(const uint64_t *__restrict__ cand, const uint32_t *__restrict__ ctl,
+                                                   const bnf_stream_desc *__restrict__ sd, uint32_t nstreams,
+                                                   uint32_t *__restrict__ clo, uint32_t *__restrict__ chi) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= nstreams) return;
+    const uint32_t n = ms_n(ctl);
+    uint32_t lo = 0, hi = 0;
+    if (n) { /* n == 0: the table may be bad */
+        const bnf_stream_desc d = sd[s];
+        lo = ms_lower(cand, n, d.begin);
+        hi = d.end - d.begin >= 2u ? ms_lower(cand, n, d.end - 1u) : lo;
+    }
+    clo[s] = lo;
+    chi[s] = hi;
+}
+
+/* seg[i]: the stream candidate i belongs to, -1 for none (chi ascends with the streams) */
+__global__ void __launch_bounds__(256) k_ms_owner(const uint32_t *__restrict__ ctl, const uint32_t *__restrict__ clo,
+                                                  const uint32_t *__restrict__ chi, uint32_t nstreams,
+                                                  int32_t *__restrict__ seg) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ms_n(ctl)) return;
+    uint32_t lo = 0, hi = nstreams; /* the first stream with chi > i */
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (chi[mid] <= i) lo = mid + 1u;
+        else hi = mid;
+    }
+    seg[i] = (lo < nstreams && clo[lo] <= i) ? (int32_t)lo : -1;
+}
+
+/* parse_frame over the candidates that belong to a stream, the count read on the device */
+__global__ void __launch_bounds__(64) k_ms_parse(const uint32_t *__restrict__ words, uint64_t nbytes,
+                                                 const uint64_t *__restrict__ cand, const uint32_t *__restrict__ ctl,
+                                                 bnf_stream_params sp, const int32_t *__restrict__ seg,
+                                                 bnf_frame_info *__restrict__ info) {
+    __shared__ LDS_DMA_ALIGN uint32_t ring[PARSE_RD * RING_LANE_DW];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x, n = ms_n(ctl);
+    if (blockIdx.x * 64u >= n) return;
+    const bool mine = i < n && seg[i] >= 0;
+    parse_frame<0>(words, nbytes, cand, n, sp, nullptr, 0, info, 0u, (lds_u32 *)ring, mine ? i : ~0u, nullptr);
+}
+
+/* k_gap_crc with the count read on the device */
+__global__ void __launch_bounds__(256) k_ms_gap_crc(const uint8_t *__restrict__ bytes, uint64_t nbytes,
+                                                    const uint64_t *__restrict__ cand, const uint32_t *__restrict__ ctl,
+                                                    uint32_t *__restrict__ gap_w) {
+    __shared__ uint16_t tab[8 * 256];
+    const uint32_t ncand = ms_n(ctl);
+    if (blockIdx.x * 4u >= ncand) return; /* the whole workgroup */
+    for (uint32_t i = threadIdx.x; i < 8u * 256u; i += 256u) tab[i] = (&g_crc16_tab[0][0])[i];
+    __syncthreads();
+    const lds_u16 *T = (const lds_u16 *)(lds_u32 *)tab;
+    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (g >= ncand) return;
+    const uint64_t b0 = cand[g];
+    const uint64_t b1 = g + 1 < ncand ? cand[g + 1] : nbytes;
+    const uint64_t slice = ((b1 - b0 + 63u) / 64u + 15u) & ~15ull;
+    const uint64_t s0 = min(b1, b0 + slice * lane);
+    const uint64_t s1 = min(b1, s0 + slice);
+    uint32_t c = s0 < s1 ? crc16_shift(crc16_range(bytes, s0, s1, T), nbytes - s1) : 0u;
+    for (int o = 32; o > 0; o >>= 1) c ^= __shfl_xor(c, o);
+    if (lane == 0) gap_w[g] = c;
+}
+
+/* k_chain_succ inside the stream's range; head[s]: the stream's first valid candidate at or
+ * after its first_offset (preset to INT_MAX).  Nearly every valid candidate lies past its
+ * stream's first_offset, and a wave's candidates nearly always belong to one stream: the
+ * wave's lowest such lane then speaks for all of them, one atomicMin per wave instead of
+ * thousands on the same address (measured: 267 -> 19 us of this kernel on 64 C2 streams). */
+__global__ void __launch_bounds__(256) k_ms_succ(const uint64_t *__restrict__ cand, const uint32_t *__restrict__ ctl,
+                                                 const uint32_t *__restrict__ key, const int32_t *__restrict__ seg,
+                                                 const bnf_stream_desc *__restrict__ sd, const uint32_t *__restrict__ chi,
+                                                 int32_t *__restrict__ succ, int32_t *__restrict__ head) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool live = i < ms_n(ctl); /* no early return: the wave votes below */
+    const uint32_t want = live ? key[i] : 0u;
+    const bool valid = (want & KEY_OK) != 0u;
+    const int32_t s = valid ? seg[i] : -1;
+    const bool after = valid && cand[i] >= sd[s].first_offset; /* a head candidate */
+    const uint64_t votes = __ballot(after);
+    if (votes) { /* wave-uniform */
+        const int first = __ffsll((unsigned long long)votes) - 1; /* the lowest lane: the lowest index */
+        const int32_t s_first = __shfl(s, first);
+        if (__ballot(after && s != s_first) == 0ull) {
+            if ((int)lane == first) atomicMin(&head[s], (int32_t)i);
+        } else if (after) {
+            atomicMin(&head[s], (int32_t)i);
+        }
+    }
+    if (!live) return;
+    int32_t r = -1;
+    if (valid) {
+        const uint32_t jend = (uint32_t)min((uint64_t)chi[s], (uint64_t)i + 1u + CHAIN_WIN);
+        for (uint32_t j = i + 1; j < jend; j++)
+            if (key[j] == want) {
+                r = (int32_t)j;
+                break;
+            }
+    }
+    succ[i] = r;
+}
+
+__global__ void __launch_bounds__(256) k_ms_mark_heads(const int32_t *__restrict__ head, uint32_t nstreams,
+                                                       const uint32_t *__restrict__ ctl, uint32_t *__restrict__ mark) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= nstreams) return;
+    const int32_t h = head[s];
+    if (h >= 0 && (uint32_t)h < ms_n(ctl)) mark[h] = 1u;
+}
+
+/* One level of the pointer doubling: src = succ^(2^k).  The marked set {succ^t(head) : t < 2^k}
+ * grows to t < 2^(k+1) (a mark set during the launch only adds further chain members, as in
+ * k_chain_mark), and dst = succ^(2^(k+1)). */
+__global__ void __launch_bounds__(256) k_ms_jump_mark(const int32_t *__restrict__ src, int32_t *__restrict__ dst,
+                                                      uint32_t *__restrict__ mark, const uint32_t *__restrict__ ctl) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ms_n(ctl)) return;
+    const int32_t a = src[i];
+    dst[i] = a < 0 ? -1 : src[a];
+    if (a >= 0 && mark[i]) mark[a] = 1u;
+}
+
+/* the blocksizes of the marked candidates, 0 for the others */
+__global__ void __launch_bounds__(256) k_ms_bs(const bnf_frame_info *__restrict__ info, const uint32_t *__restrict__ mark,
+                                               const uint32_t *__restrict__ ctl, uint64_t *__restrict__ bs) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ms_n(ctl)) return;
+    bs[i] = mark[i] ? info[i].blocksize : 0u;
+}
+
+/* kept[s] = the stream's chain length (pos: exclusive prefix of mark, n + 1 entries) */
+__global__ void __launch_bounds__(256) k_ms_kept_init(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ clo,
+                                                      const uint32_t *__restrict__ chi, uint32_t nstreams,
+                                                      uint32_t *__restrict__ kept) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= nstreams) return;
+    kept[s] = pos[chi[s]] - pos[clo[s]];
+}
+
+/* the EOS rule per stream (k_chain_emit's): kept[s] = min(chain length, first position whose
+ * stream-local sample count is at or past the stream's total_samples) */
+__global__ void __launch_bounds__(256) k_ms_eos(const uint32_t *__restrict__ ctl, const uint32_t *__restrict__ mark,
+                                                const int32_t *__restrict__ seg, const uint32_t *__restrict__ clo,
+                                                const uint32_t *__restrict__ pos, const uint64_t *__restrict__ smp,
+                                                const bnf_stream_desc *__restrict__ sd, bnf_stream_params sp,
+                                                uint32_t *__restrict__ kept) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ms_n(ctl) || !mark[i] || !sp.has_stream_info) return;
+    const int32_t s = seg[i];
+    const uint64_t total = sd[s].total_samples;
+    const uint32_t c0 = clo[s];
+    if (total > 0 && smp[i] - smp[c0] >= total) atomicMin(&kept[s], pos[i] - pos[c0]);
+}
+
+/* ssum[s]: the samples of the stream's kept frames -- the local sample count of the first
+ * dropped frame, or of the chain's end when none is dropped */
+__global__ void __launch_bounds__(256) k_ms_ssum(const uint32_t *__restrict__ ctl, const uint32_t *__restrict__ mark,
+                                                 const int32_t *__restrict__ seg, const uint32_t *__restrict__ clo,
+                                                 const uint32_t *__restrict__ chi, const uint32_t *__restrict__ pos,
+                                                 const uint64_t *__restrict__ smp, const uint32_t *__restrict__ kept,
+                                                 uint32_t nstreams, uint64_t *__restrict__ ssum) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nstreams && kept[i] == pos[chi[i]] - pos[clo[i]]) ssum[i] = smp[chi[i]] - smp[clo[i]];
+    if (i >= ms_n(ctl) || !mark[i]) return;
+    const int32_t s = seg[i];
+    const uint32_t c0 = clo[s];
+    if (pos[i] - pos[c0] == kept[s]) ssum[s] = smp[i] - smp[c0];
+}
+
+/* outputs in stream order: sf / ss are the exclusive prefixes of kept / ssum over the streams */
+__global__ void __launch_bounds__(256) k_ms_emit(const uint64_t *__restrict__ cand, const uint32_t *__restrict__ ctl,
+                                                 const bnf_frame_info *__restrict__ info, const uint32_t *__restrict__ mark,
+                                                 const int32_t *__restrict__ seg, const uint32_t *__restrict__ clo,
+                                                 const uint32_t *__restrict__ pos, const uint64_t *__restrict__ smp,
+                                                 const uint32_t *__restrict__ kept, const uint32_t *__restrict__ sf,
+                                                 const uint64_t *__restrict__ ss, uint64_t *__restrict__ d_offs,
+                                                 uint64_t *__restrict__ d_os, bnf_frame_info *__restrict__ d_info,
+                                                 uint32_t cap) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ms_n(ctl) || !mark[i]) return;
+    const int32_t s = seg[i];
+    const uint32_t c0 = clo[s], lp = pos[i] - pos[c0];
+    if (lp >= kept[s]) return;
+    const uint32_t p = sf[s] + lp;
+    if (p >= cap) return;
+    const uint64_t os = ss[s] + (smp[i] - smp[c0]);
+    d_offs[p] = cand[i];
+    if (d_os) d_os[p] = os;
+    if (d_info) {
+        bnf_frame_info fi = info[i];
+        fi.out_sample = os;
+        d_info[p] = fi;
+    }
+}
+
+__global__ void k_ms_status(const uint32_t *__restrict__ ctl, uint32_t cand_cap, const uint32_t *__restrict__ sf,
+                            uint32_t nstreams, uint32_t cap, uint32_t *__restrict__ status) {
+    const uint32_t total = sf[nstreams];
+    status[0] = (ctl[MS_NCAND] > cand_cap ? 1u : 0u) | (total > cap ? 2u : 0u) | (ctl[MS_BAD] ? 4u : 0u);
+    status[1] = ctl[MS_NCAND];
+    status[2] = total;
+    status[3] = 0u;
+}
 #endif /* BNF_TU == 0 */
 
 #if BNF_TU == 3 || BNF_TU == 4 || BNF_TU == 7 /* TU 7: k_decode_sw, on the same helpers */
@@ -5486,6 +5910,72 @@ hipError_t bnf_launch_chain(const uint8_t *bytes, uint64_t nbytes, const uint64_
     if (ncand)
         hipLaunchKernelGGL(k_chain_emit, g256, dim3(256), 0, s, cand, ncand, info, mark, pos, bs, sp, d_offs, d_os,
                            d_info, cap, nframes);
+    return hipGetLastError();
+}
+
+/* exclusive prefixes of c[0, n) (and a[0, n) when a != nullptr) into co / ao (n + 1 entries);
+ * n = min(*n_ptr, cap), or cap when n_ptr is null.  co may be c. */
+static void ms_scan_add(const uint32_t *c, const uint64_t *a, const uint32_t *n_ptr, uint32_t cap, uint32_t *csum,
+                        uint64_t *asum, uint32_t *co, uint64_t *ao, hipStream_t s) {
+    const uint32_t nb = cap / MS_SCAN + 1u; /* covers element `cap` (the total) */
+    hipLaunchKernelGGL(k_ms_add_reduce, dim3(nb), dim3(MS_SCAN), 0, s, c, a, n_ptr, cap, csum, a ? asum : nullptr);
+    hipLaunchKernelGGL(k_ms_add_sums, dim3(1), dim3(MS_SCAN), 0, s, csum, a ? asum : nullptr, nb);
+    hipLaunchKernelGGL(k_ms_add_apply, dim3(nb), dim3(MS_SCAN), 0, s, c, a, n_ptr, cap, csum, asum, co, ao);
+}
+
+/* The batched frame chain (see k_ms_check): sync scan, parse, keys, successors, pointer
+ * doubling, EOS rule per stream and outputs, with no host synchronisation.  d_sf (nstreams + 1)
+ * and d_status (4) are always written; d_ss may be null. */
+hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
+                                    bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
+                                    uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
+                                    uint32_t *d_status, hipStream_t s) {
+    const uint32_t C = cand_cap, S = nstreams;
+    const uint32_t B = bnf_scan_blocks(nbytes);
+    const dim3 gc((C + 255u) / 256u), gs((S + 255u) / 256u), t256(256);
+    const uint32_t *ctl = w.ctl;
+    hipError_t e = hipMemsetAsync(w.ctl, 0, sizeof(uint32_t) * MS_CTL_WORDS, s);
+    if (e == hipSuccess) e = hipMemsetAsync(w.head, 0x7f, sizeof(int32_t) * (size_t)S, s);
+    if (e == hipSuccess) e = hipMemsetAsync(w.mark, 0, sizeof(uint32_t) * (size_t)C, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ms_check, gs, t256, 0, s, sd, S, nbytes, w.ctl);
+    /* 1. sync candidates of the whole buffer */
+    hipLaunchKernelGGL(k_ms_sync<0>, dim3(B), t256, 0, s, bytes, nbytes, w.blk, (uint64_t *)nullptr, 0u);
+    ms_scan_add(w.blk, nullptr, nullptr, B, w.csum, w.asum, w.blk, nullptr, s);
+    hipLaunchKernelGGL(k_ms_set_n, dim3(1), dim3(1), 0, s, w.blk + B, C, w.ctl);
+    hipLaunchKernelGGL(k_ms_sync<1>, dim3(B), t256, 0, s, bytes, nbytes, w.blk, w.cand, C);
+    /* 2. owners, then header, CRC-8 and subframe walk of every owned candidate */
+    hipLaunchKernelGGL(k_ms_ranges, gs, t256, 0, s, w.cand, ctl, sd, S, w.clo, w.chi);
+    hipLaunchKernelGGL(k_ms_owner, gc, t256, 0, s, ctl, w.clo, w.chi, S, w.seg);
+    hipLaunchKernelGGL(k_ms_parse, dim3((C + 63u) / 64u), dim3(64), 0, s, (const uint32_t *)bytes, nbytes, w.cand, ctl, sp,
+                       w.seg, w.info);
+    /* 3. keys, successors, heads */
+    const uint32_t nbc = (C + MS_SCAN - 1u) / MS_SCAN;
+    hipLaunchKernelGGL(k_ms_gap_crc, dim3((C + 3u) / 4u), t256, 0, s, bytes, nbytes, w.cand, ctl, w.key);
+    hipLaunchKernelGGL(k_ms_keys_reduce, dim3(nbc), dim3(MS_SCAN), 0, s, w.key, ctl, w.csum);
+    hipLaunchKernelGGL(k_ms_keys_sums, dim3(1), dim3(MS_SCAN), 0, s, w.csum, nbc);
+    hipLaunchKernelGGL(k_ms_keys_apply, dim3(nbc), dim3(MS_SCAN), 0, s, w.key, ctl, w.csum, w.info, w.seg, sd);
+    hipLaunchKernelGGL(k_ms_succ, gc, t256, 0, s, w.cand, ctl, w.key, w.seg, sd, w.chi, w.jump, w.head);
+    hipLaunchKernelGGL(k_ms_mark_heads, gs, t256, 0, s, w.head, S, ctl, w.mark);
+    /* 4. pointer doubling over all chains at once: 2^levels >= cand_cap */
+    uint32_t levels = 1;
+    while ((1ull << levels) < C) levels++;
+    for (uint32_t k = 0; k < levels; k++)
+        hipLaunchKernelGGL(k_ms_jump_mark, gc, t256, 0, s, w.jump + (size_t)(k & 1u) * C, w.jump + (size_t)((k + 1u) & 1u) * C,
+                           w.mark, ctl);
+    /* 5. positions and sample counts, kept frames per stream, the two prefixes over the streams */
+    hipLaunchKernelGGL(k_ms_bs, gc, t256, 0, s, w.info, w.mark, ctl, w.bs);
+    ms_scan_add(w.mark, w.bs, ctl + MS_N, C, w.csum, w.asum, w.pos, w.smp, s);
+    hipLaunchKernelGGL(k_ms_kept_init, gs, t256, 0, s, w.pos, w.clo, w.chi, S, w.kept);
+    hipLaunchKernelGGL(k_ms_eos, gc, t256, 0, s, ctl, w.mark, w.seg, w.clo, w.pos, w.smp, sd, sp, w.kept);
+    hipLaunchKernelGGL(k_ms_ssum, dim3((std::max(C, S) + 255u) / 256u), t256, 0, s, ctl, w.mark, w.seg, w.clo, w.chi, w.pos,
+                       w.smp, w.kept, S, w.ssum);
+    uint64_t *ss = d_ss ? d_ss : w.ss;
+    ms_scan_add(w.kept, w.ssum, nullptr, S, w.csum, w.asum, d_sf, ss, s);
+    /* 6. outputs */
+    hipLaunchKernelGGL(k_ms_emit, gc, t256, 0, s, w.cand, ctl, w.info, w.mark, w.seg, w.clo, w.pos, w.smp, w.kept, d_sf, ss,
+                       d_offs, d_os, d_info, cap);
+    hipLaunchKernelGGL(k_ms_status, dim3(1), dim3(1), 0, s, ctl, C, d_sf, S, cap, d_status);
     return hipGetLastError();
 }
 

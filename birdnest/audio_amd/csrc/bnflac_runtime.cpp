@@ -58,6 +58,10 @@ hipError_t bnf_launch_chain(const uint8_t *bytes, uint64_t nbytes, const uint64_
                             int32_t *jump, uint32_t levels, uint32_t *mark, uint32_t *pos, uint64_t *bs, uint8_t *small,
                             uint64_t *d_offs, uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *nframes,
                             hipStream_t s);
+hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
+                                    bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
+                                    uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
+                                    uint32_t *d_status, hipStream_t s);
 }
 
 /* ------------------------------------------------------------------ errors */
@@ -202,6 +206,7 @@ struct bnflac_ctx {
     uint32_t block_cap = 0;
     /* bnflac_index_stream scratch */
     CtxBuf cand, info, gap, jump, mark, pos, bs, small;
+    CtxBuf ms; /* bnflac_index_streams scratch (bnf_ms_scratch, one allocation) */
     CtxBuf order, porder; /* decode / parse order: histogram + permutation (k_order_*) */
     /* k_parse's CRC-16 hand-off of the last bnflac_parse_frames batch (8 words per frame), and
      * the batch they belong to: bnflac_decode_parsed uses them only for that same batch */
@@ -239,7 +244,7 @@ extern "C" BNFLAC_API void bnflac_ctx_destroy(bnflac_ctx *ctx) {
     if (!ctx) return;
     if (ctx->d_block_counts) (void)hipFree(ctx->d_block_counts);
     for (CtxBuf *b : {&ctx->cand, &ctx->info, &ctx->gap, &ctx->jump, &ctx->mark, &ctx->pos, &ctx->bs, &ctx->small,
-                      &ctx->order, &ctx->porder, &ctx->crcp})
+                      &ctx->ms, &ctx->order, &ctx->porder, &ctx->crcp})
         b->release();
     delete ctx;
 }
@@ -403,6 +408,75 @@ extern "C" BNFLAC_API int bnflac_index_stream(bnflac_ctx *ctx, const uint8_t *d_
                              (uint8_t *)ctx->small.p + 16, d_frame_offsets, d_out_sample, (bnf_frame_info *)d_info, cap,
                              d_nframes, s);
     return e == hipSuccess ? 0 : fail(std::string("bnflac_index_stream: ") + hipGetErrorString(e));
+}
+
+static_assert(sizeof(bnflac_stream_desc) == sizeof(bnf_stream_desc), "stream descriptor layout");
+
+extern "C" BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
+                                               const bnflac_stream_desc *d_streams, uint32_t nstreams,
+                                               const bnflac_stream_params *sp, uint32_t cand_cap,
+                                               uint64_t *d_frame_offsets, uint64_t *d_out_sample,
+                                               bnflac_frame_info *d_info, uint32_t cap, uint32_t *d_stream_frames,
+                                               uint64_t *d_stream_samples, uint32_t *d_status, void *hs) {
+    if (check_args(ctx, d_bytes, nbytes, sp, "bnflac_index_streams")) return -1;
+    DevGuard dg(ctx->device); /* launches and scratch on the context's device */
+    if (!d_stream_frames || !d_status || (cap && !d_frame_offsets)) return fail("bnflac_index_streams: null output");
+    if (nstreams && !d_streams) return fail("bnflac_index_streams: null descriptor table");
+    if (nstreams >= (1u << 30)) return fail("bnflac_index_streams: too many streams");
+    hipStream_t s = (hipStream_t)hs;
+    ctx->crcp_bytes = ctx->crcp_info = nullptr; /* the records this writes carry no CRC-16 hand-off */
+    if (!nstreams || !nbytes) { /* nothing to index: zeros */
+        hipError_t e = hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_stream_frames, 0, sizeof(uint32_t) * ((size_t)nstreams + 1), s);
+        if (e == hipSuccess && d_stream_samples)
+            e = hipMemsetAsync(d_stream_samples, 0, sizeof(uint64_t) * ((size_t)nstreams + 1), s);
+        return e == hipSuccess ? 0 : fail(std::string("bnflac_index_streams: ") + hipGetErrorString(e));
+    }
+    const uint64_t C64 = cand_cap ? cand_cap : nbytes / 1024 + 4096;
+    if (C64 >= (1u << 30)) return fail("bnflac_index_streams: cand_cap too large");
+    /* scratch, sized on the host from cand_cap, nstreams and nbytes: every array starts on a
+     * 16-byte boundary of one allocation */
+    const size_t C = (size_t)C64, S = nstreams, B = bnf_scan_blocks(nbytes);
+    const size_t nsum = std::max(B, std::max(C, S)) / 1024 + 2;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t o_ctl = take(16), o_blk = take(4 * (B + 1)), o_csum = take(4 * nsum), o_asum = take(8 * nsum),
+                 o_cand = take(8 * C), o_info = take(sizeof(bnf_frame_info) * C), o_seg = take(4 * C), o_key = take(4 * C),
+                 o_mark = take(4 * C), o_pos = take(4 * (C + 1)), o_bs = take(8 * C), o_smp = take(8 * (C + 1)),
+                 o_jump = take(8 * C), o_clo = take(4 * S), o_chi = take(4 * S), o_kept = take(4 * S), o_head = take(4 * S),
+                 o_ssum = take(8 * S), o_ss = take(8 * (S + 1));
+    if (!ctx->ms.grow(off)) return fail("bnflac_index_streams: out of device memory");
+    uint8_t *m = (uint8_t *)ctx->ms.p;
+    bnf_ms_scratch w;
+    w.ctl = (uint32_t *)(m + o_ctl);
+    w.blk = (uint32_t *)(m + o_blk);
+    w.csum = (uint32_t *)(m + o_csum);
+    w.asum = (uint64_t *)(m + o_asum);
+    w.cand = (uint64_t *)(m + o_cand);
+    w.info = (bnf_frame_info *)(m + o_info);
+    w.seg = (int32_t *)(m + o_seg);
+    w.key = (uint32_t *)(m + o_key);
+    w.mark = (uint32_t *)(m + o_mark);
+    w.pos = (uint32_t *)(m + o_pos);
+    w.bs = (uint64_t *)(m + o_bs);
+    w.smp = (uint64_t *)(m + o_smp);
+    w.jump = (int32_t *)(m + o_jump);
+    w.clo = (uint32_t *)(m + o_clo);
+    w.chi = (uint32_t *)(m + o_chi);
+    w.kept = (uint32_t *)(m + o_kept);
+    w.head = (int32_t *)(m + o_head);
+    w.ssum = (uint64_t *)(m + o_ssum);
+    w.ss = (uint64_t *)(m + o_ss);
+    bnf_stream_params p;
+    memcpy(&p, sp, sizeof p);
+    hipError_t e = bnf_launch_chain_streams(d_bytes, nbytes, (const bnf_stream_desc *)d_streams, nstreams, p, (uint32_t)C, w,
+                                            d_frame_offsets, d_out_sample, (bnf_frame_info *)d_info, cap, d_stream_frames,
+                                            d_stream_samples, d_status, s);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_index_streams: ") + hipGetErrorString(e));
 }
 
 /* ====================================================================== */

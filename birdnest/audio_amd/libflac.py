@@ -126,6 +126,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_index_frames", "bnflac_decode_frames", "bnflac_parse_frames", "bnflac_decode_parsed",
                  "bnflac_out_stride", "bnflac_debug_set_ablate", "bnflac_debug_stats", "bnflac_debug_set_parse_wave", "bnflac_debug_parse_wave_stats",
                  "bnflac_debug_set_decode_sys", "bnflac_debug_decode_seg_launches", "bnflac_md5_interleaved32", "bnflac_index_stream",
+                 "bnflac_index_streams",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -192,6 +193,9 @@ def load() -> ctypes.CDLL:
     L.FLAC__stream_decoder_get_md5_checking.argtypes = [p]
     L.bnflac_index_stream.restype = i
     L.bnflac_index_stream.argtypes = [p, p, ctypes.c_uint64, ctypes.c_uint64, p, p, p, p, ctypes.c_uint32, p, p]
+    L.bnflac_index_streams.restype = i
+    L.bnflac_index_streams.argtypes = [p, p, ctypes.c_uint64, p, ctypes.c_uint32, p, ctypes.c_uint32, p, p, p,
+                                       ctypes.c_uint32, p, p, p, p]
     L.bnflac_reader_open.restype = i
     L.bnflac_reader_open.argtypes = [i, p, ctypes.c_uint64, i, ctypes.c_uint32, ctypes.POINTER(p)]
     L.bnflac_reader_params.restype = i
@@ -317,6 +321,36 @@ class StreamParams(ctypes.Structure):
         return cls(1, mn, mx, p.sample_rate, p.channels, p.bps, total_samples)
 
 
+class StreamDesc(ctypes.Structure):
+    """bnflac_stream_desc: one stream of an index_streams batch."""
+    _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("first_offset", ctypes.c_uint64),
+                ("total_samples", ctypes.c_uint64)]
+
+
+STREAM_DESC_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("first_offset", "<u8"), ("total_samples", "<u8")])
+assert STREAM_DESC_DTYPE.itemsize == ctypes.sizeof(StreamDesc)
+
+
+def stream_table(streams, nbytes: int) -> np.ndarray:
+    """The descriptor table of index_streams from [(begin, end, first_offset, total_samples)],
+    checked as the library checks it (its status bit 2): ValueError for a range that is
+    reversed, past nbytes, out of order or overlapping, or a first_offset outside its range."""
+    table = np.zeros(len(streams), dtype=STREAM_DESC_DTYPE)
+    prev_end = 0
+    for k, (begin, end, first, total) in enumerate(streams):
+        if not 0 <= begin <= end <= nbytes:
+            raise ValueError(f"stream {k}: range [{begin}, {end}) is not inside the buffer of {nbytes} bytes")
+        if not begin <= first <= end:
+            raise ValueError(f"stream {k}: first_offset {first} is outside [{begin}, {end}]")
+        if begin < prev_end:
+            raise ValueError(f"stream {k}: range [{begin}, {end}) overlaps or precedes the previous stream's")
+        if total < 0:
+            raise ValueError(f"stream {k}: negative total_samples")
+        prev_end = end
+        table[k] = (begin, end, first, total)
+    return table
+
+
 def out_stride(fmt: int, sp: StreamParams) -> int:
     return int(load().bnflac_out_stride(fmt, ctypes.byref(sp)))
 
@@ -387,6 +421,35 @@ class BatchDecoder:
         s = stream if stream is not None else torch.cuda.current_stream()
         s.synchronize()
         return d_offs, d_os, d_info, int(d_n.item())
+
+    def index_streams(self, d_bytes, nbytes: int, streams, sp: StreamParams, cap: int, cand_cap: int = 0, stream=None):
+        """Frame chains of many streams held in one buffer (bnflac_index_streams), one call.
+        streams: [(begin, end, first_offset, total_samples)], ascending and non-overlapping.
+        -> (d_offsets int64[cap], d_out_sample int64[cap], d_info uint8[cap*128],
+            d_stream_frames int32[n+1], d_stream_samples int64[n+1], d_status int32[4]),
+        all on the device and not synchronised: the caller does that, as for decode_parsed."""
+        import torch
+        table = stream_table(streams, nbytes)
+        dev = d_bytes.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        n = len(table)
+        with torch.cuda.stream(s):
+            d_tab = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev) if n else None
+            d_offs = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+            d_os = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+            d_info = torch.zeros(max(cap, 1) * FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
+            d_sf = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+            d_ss = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        rc = self.L.bnflac_index_streams(self.ctx, ctypes.c_void_p(d_bytes.data_ptr()), nbytes,
+                                         ctypes.c_void_p(d_tab.data_ptr()) if n else None, n, ctypes.byref(sp), cand_cap,
+                                         ctypes.c_void_p(d_offs.data_ptr()), ctypes.c_void_p(d_os.data_ptr()),
+                                         ctypes.c_void_p(d_info.data_ptr()), cap, ctypes.c_void_p(d_sf.data_ptr()),
+                                         ctypes.c_void_p(d_ss.data_ptr()), ctypes.c_void_p(d_status.data_ptr()),
+                                         self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_offs, d_os, d_info, d_sf, d_ss, d_status
 
     def decode_frames(self, d_bytes, nbytes: int, d_offsets, nframes: int, sp: StreamParams, fmt: int, d_out,
                       d_info, d_out_sample=None, base_sample: int = 0, stream=None, out_bytes=None):

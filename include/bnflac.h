@@ -150,6 +150,41 @@ BNFLAC_API int bnflac_index_stream(bnflac_ctx *ctx, const uint8_t *d_bytes, uint
                                    const bnflac_stream_params *sp, uint64_t *d_frame_offsets, uint64_t *d_out_sample,
                                    bnflac_frame_info *d_info, uint32_t cap, uint32_t *d_nframes, void *hip_stream);
 
+/* One stream of a bnflac_index_streams batch.  The table is device-resident, one entry per
+ * stream, ascending and non-overlapping. */
+typedef struct {
+    uint64_t begin, end;    /* the stream's bytes are d_bytes[begin, end); begin needs no alignment */
+    uint64_t first_offset;  /* absolute offset in d_bytes of the byte after the metadata blocks */
+    uint64_t total_samples; /* STREAMINFO total for the end-of-stream rule; 0 = unknown (no rule) */
+} bnflac_stream_desc;
+
+/* bnflac_index_stream for many streams held in one buffer, in one call and with no host
+ * synchronisation.  Stream s contributes exactly the frames bnflac_index_stream returns for
+ * d_bytes[begin, end) alone with first_offset - begin and that stream's total_samples; sp is
+ * shared by the batch (its total_samples is ignored).  The frames are concatenated in stream
+ * order: stream s owns positions [d_stream_frames[s], d_stream_frames[s + 1]) of
+ * d_frame_offsets (absolute offsets into d_bytes), d_out_sample (may be NULL: position in the
+ * concatenated PCM, d_stream_samples[s] plus the stream's running sample count) and d_info
+ * (may be NULL: the records with that out_sample, ready for one bnflac_decode_parsed over the
+ * whole buffer).  d_stream_frames and d_stream_samples (may be NULL) have nstreams + 1
+ * entries: the exclusive prefixes of the frames and samples kept per stream.  Only positions
+ * below cap are written; d_stream_frames[nstreams] is the true total.
+ * cand_cap bounds the sync candidates of the whole buffer (0: nbytes / 1024 + 4096) and sizes
+ * the context's scratch, which a call may have to allocate.
+ * d_status (device, 4 words): [0] flags -- bit 0 more candidates than cand_cap (outputs
+ * unspecified, d_stream_frames all zero; retry with cand_cap = word 1), bit 1 more frames
+ * than cap, bit 2 malformed table (begin > end, end > nbytes, first_offset outside
+ * [begin, end], or out of order; outputs as for bit 0); [1] candidates found; [2] frames in
+ * total; [3] 0.  nstreams == 0 or nbytes == 0 writes zeros.  A stream cut within the last
+ * subframe's first byte of its last frame keeps that frame, with decode-class flags that
+ * depend on the byte after the cut.  Asynchronous on hip_stream. */
+BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
+                                    const bnflac_stream_desc *d_streams, uint32_t nstreams,
+                                    const bnflac_stream_params *sp, uint32_t cand_cap, uint64_t *d_frame_offsets,
+                                    uint64_t *d_out_sample, bnflac_frame_info *d_info, uint32_t cap,
+                                    uint32_t *d_stream_frames, uint64_t *d_stream_samples, uint32_t *d_status,
+                                    void *hip_stream);
+
 /* Decode nframes frames starting at d_frame_offsets (byte offsets into d_bytes).
  * Output position of each frame: d_out_sample[i] if non-NULL, else the header's
  * sample number (frame number x STREAMINFO blocksize for fixed-blocksize streams) minus
@@ -170,7 +205,7 @@ BNFLAC_API int bnflac_decode_frames(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
  * decorrelation, packing and CRC-16 (k_decode).  decode must follow parse on the same
  * stream with the same arguments.  The parse also does part of the CRC-16 work of 2-channel
  * frames and hands it to the next bnflac_decode_parsed call on the same ctx with the same
- * d_bytes, nbytes, d_info and nframes (used once; bnflac_index_stream drops it): the frame
+ * d_bytes, nbytes, d_info and nframes (used once; bnflac_index_stream and bnflac_index_streams drop it): the frame
  * bytes must not change between the two calls (bnflac_debug_set_crc_mode). */
 BNFLAC_API int bnflac_parse_frames(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
                                    const uint64_t *d_frame_offsets, uint32_t nframes,
