@@ -1036,6 +1036,51 @@ DEV void pk_resync(BR &b, uint32_t lane) {
     b.vlim = b.vendw - 1u;
 }
 DEV void pk_next_word(BR &b) { b.nx = *(const lds_u32 *)((const __attribute__((address_space(3))) uint8_t *)b.ring + b.ra); }
+/* The walk's refill, in 64-byte groups (k_decode_st's st_refill_issue form).  The 8-slot ring
+ * holds two groups; a lane whose cursor (word wi) has entered the newer one (iend == cg + 4)
+ * fetches group iend into the older group's four rows: one address, the four blocks by
+ * immediate offset, and a row group is issued only when some lane wants it.  br_refill fetches
+ * the same blocks ([max(iend, cg), cg + 8), the line of word wi kept) with a rotation, a
+ * compare, a clamp and a 64-bit address per slot, for all 8 slots on every call.  The walk
+ * issues no stores, so vmcnt(0) waits for exactly the DMAs of the refill before.  The group
+ * form moves one group: when any lane's cursor is outside the ring's two groups (after
+ * br_skip over an escaped partition, the generic readers of the rare paths, candidate frames
+ * of arbitrary bytes) the whole wave takes br_refill, which catches up any distance.
+ * BNF_ABLATE_PARSE_BLKREFILL: br_refill always (the exact A/B switch). */
+#define BNF_ABLATE_PARSE_BLKREFILL 0x800000u
+DEV void pk_refill(BR &b, uint32_t ablate) {
+    const uint32_t cg = (b.wi >> 2) & ~3u; /* first block of the cursor's group */
+    /* iend and cg are multiples of 4: in the ring iff iend is cg + 4 or cg + 8 */
+    if (__builtin_expect(any_lane(b.iend - cg - 4u > 4u) || (ablate & BNF_ABLATE_PARSE_BLKREFILL), 0)) {
+        br_refill(b);
+        return;
+    }
+    wait_vm();
+    b.vendw = b.iend * 4u;
+    const bool go = b.iend == cg + 4u;
+    const uint32_t h = b.iend & 4u;          /* the free group's slots: 0-3 or 4-7 */
+    const bool whole = b.iend + 3u < b.nblk; /* else the buffer's last blocks, clamped */
+    const uint32_t *a = b.w + (uint64_t)b.iend * 4u;
+#pragma unroll
+    for (int g = 0; g < 2; g++) {
+        const bool gg = go && h == 4u * (uint32_t)g;
+        if (any_lane(gg)) {
+            if (gg) {
+                lds_u32 *row = b.ring + 4u * (uint32_t)g * RING_LANE_DW;
+                if (__builtin_expect(whole, 1)) {
+                    lds_dma16_off<0>(a, row);
+                    lds_dma16_off<16>(a, row + RING_LANE_DW);
+                    lds_dma16_off<32>(a, row + 2 * RING_LANE_DW);
+                    lds_dma16_off<48>(a, row + 3 * RING_LANE_DW);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) dma_block(b, b.iend + (uint32_t)k, 4u * (uint32_t)g + (uint32_t)k);
+                }
+            }
+        }
+    }
+    if (go) b.iend += 4u;
+}
 DEV void pk_step(BR &b, uint32_t &rem, uint32_t k1, bool &stall, uint32_t laneb) {
     const bool live = rem != 0u;
     const uint32_t w = br_peek(b);
@@ -1089,14 +1134,14 @@ DEV uint32_t skip_residual_t(BR &b, const SubHdr &h, uint32_t bs, uint64_t limit
         if (BULK) {
             if (__builtin_amdgcn_readfirstlane(since) >= 12u && !(ablate & 32u)) { /* every 12-14 steps */
                 if (CP) crcp_hook(cp, b, lane, b.wi >> 4); /* the lines loaded, before the refill overwrites them */
-                br_refill(b);
+                pk_refill(b, ablate);
                 pk_resync(b, lane);
                 since = 0;
             }
             since += 2u;
         } else if ((__builtin_amdgcn_readfirstlane(since++) & 7u) == 0u && !(ablate & 32u)) { /* every 16 steps */
             if (CP) crcp_hook(cp, b, lane, b.wi >> 4);
-            br_refill(b);
+            pk_refill(b, ablate);
             pk_resync(b, lane);
         }
         const bool sw = rem == 0u && p < parts;
@@ -1711,13 +1756,16 @@ DEV void parse_frame(const uint32_t *__restrict__ words, uint64_t nbytes, const 
     if (st == BNF_ST_ERROR && br_pos(b) > limit) st = BNF_ST_TRUNC;
     if (CPM && crcp != nullptr && st == BNF_ST_OK && fi.channels == 2u && !(ablate & 16u)) {
         /* the frame's first line, its bytes below frame_off cleared (L2-warm: the ring's
-         * refill just read it) */
+         * refill just read it).  Only the 16-byte blocks that start inside the 16-byte-rounded
+         * buffer are read (st_crc16_ok's tail rule), the rest taken as zeros: a line the buffer
+         * ends in holds the frame's end, and the tails do not continue a prefix past it */
         const uint32_t h = (uint32_t)(fi.frame_off & 63u);
-        const u32x4 *g = (const u32x4 *)((const uint8_t *)words + (fi.frame_off & ~(uint64_t)63u));
+        const uint64_t l0 = fi.frame_off & ~(uint64_t)63u, lend = (nbytes + 15u) & ~(uint64_t)15u;
+        const u32x4 *g = (const u32x4 *)((const uint8_t *)words + l0);
         u32x4 v[4];
 #pragma unroll
         for (uint32_t i = 0; i < 4; i++) {
-            v[i] = g[i];
+            v[i] = l0 + 16u * i < lend ? g[i] : u32x4{0u, 0u, 0u, 0u};
             v[i].x &= st_hmask(h, 16u * i);
             v[i].y &= st_hmask(h, 16u * i + 4u);
             v[i].z &= st_hmask(h, 16u * i + 8u);

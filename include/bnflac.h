@@ -222,7 +222,9 @@ BNFLAC_API int bnflac_decode_parsed(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
  * start of d_out (an L2-resident footprint); it is ignored when out_bytes < 1 MiB.
  * Bit 0x40 is an exact A/B switch (identical PCM and records): k_decode_st keeps no running
  * CRC-16 of channel 1 in its chunk loop, and its tail reads channel 1 again from k_parse's
- * prefix on, as it did before the running remainder. */
+ * prefix on, as it did before the running remainder.
+ * Bit 0x800000 is an exact A/B switch too: k_parse's residual walk refills its ring block by
+ * block (all 8 slots tested on every refill, as before the 64-byte group form). */
 BNFLAC_API void bnflac_debug_set_ablate(uint32_t flags);
 /* Debug: 1 when the library was built with -DBNFLAC_CRC_FOLD_CHECK (never the shipped one):
  * k_decode_st's tail then computes the frame's CRC-16 both from the running remainder and from
