@@ -18,10 +18,37 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
-HIP_SOURCES = [os.path.join(CSRC, "bnflac_kernels.hip"), os.path.join(CSRC, "bnflac_sys.hip"),
-               os.path.join(CSRC, "bnflac_runtime.cpp"), os.path.join(CSRC, "bnflac_reader.cpp")]
-HIP_HEADERS = [os.path.join(CSRC, "bnflac_device.h"), os.path.join(CSRC, "bnflac_md5.h"), os.path.join(INCLUDE, "bnflac.h"),
-               os.path.join(INCLUDE, "FLAC_compat.h")]
+# The translation units of libbnflac.so: (source under csrc/, extra -D flags, object name).
+# bnflac_kernels.hip is built once per BNF_TU.  This is the only description of the build: the
+# compile jobs, the staleness check and source_hash() all derive from it and from the listing
+# of csrc/ below.
+HIP_TUS = [
+    ("bnflac_kernels.hip", ["-DBNF_TU=0"], "bnflac_kernels_tu0"),  # sync scan, parse, both indexers, frame orders, the dispatcher
+    ("bnflac_kernels.hip", ["-DBNF_TU=1"], "bnflac_kernels_tu1"),  # k_decode<8>
+    ("bnflac_kernels.hip", ["-DBNF_TU=2"], "bnflac_kernels_tu2"),  # k_decode<32>, k_decode_list, k_decode_seg
+    ("bnflac_kernels.hip", ["-DBNF_TU=3"], "bnflac_kernels_tu3"),  # k_decode_st<FLACDECODER>
+    ("bnflac_kernels.hip", ["-DBNF_TU=4"], "bnflac_kernels_tu4"),  # k_decode_st<other layouts>
+    ("bnflac_kernels.hip", ["-DBNF_TU=5"], "bnflac_kernels_tu5"),  # k_decode<16>
+    ("bnflac_kernels.hip", ["-DBNF_TU=7"], "bnflac_kernels_tu7"),  # k_decode_sw
+    ("bnflac_sys.hip", [], "bnflac_sys"),  # k_decode_sys (TU 8; includes bnflac_kernels.hip)
+    ("bnflac_runtime.cpp", [], "bnflac_runtime"),
+    ("bnflac_reader.cpp", [], "bnflac_reader"),
+]
+
+
+def hip_inputs():
+    """Every file libbnflac.so can be built from: all regular files under csrc/, subdirectories
+    included (synth/ aside: that is libbnflac_synth.so), and the public headers.  A listing, so
+    a new header cannot be forgotten."""
+    files = []
+    for d, dirs, names in os.walk(CSRC):
+        if d == CSRC and "synth" in dirs:
+            dirs.remove("synth")
+        files += [os.path.join(d, f) for f in names]
+    files.sort()
+    return files + [os.path.join(INCLUDE, "bnflac.h"), os.path.join(INCLUDE, "FLAC_compat.h")]
+
+
 SYNTH_SOURCES = [os.path.join(CSRC, "synth", "bnflac_synth.c")]
 SYNTH_HEADERS = [os.path.join(CSRC, "synth", "bnflac_synth.h")]
 
@@ -40,9 +67,6 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-KERNEL_TUS = (0, 1, 2, 3, 4, 5, 7)  # one build of bnflac_kernels.hip per BNF_TU: scan+parse, k_decode<8>, k_decode<32> + k_decode_list, k_decode_st<FLACDECODER>, k_decode_st<others>, k_decode<16>, k_decode_sw (TU 8: bnflac_sys.hip)
-
-
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]
 
 
@@ -52,11 +76,11 @@ def source_hash() -> str:
     summary (profiles/traffic_*.json) is attached to a bench run only when the stamps match."""
     import hashlib
     h = hashlib.sha256()
-    for f in HIP_SOURCES + HIP_HEADERS:
-        h.update(os.path.basename(f).encode())
+    for f in hip_inputs():
+        h.update(os.path.relpath(f, ROOT).encode())
         with open(f, "rb") as fh:
             h.update(fh.read())
-    h.update(repr((KERNEL_TUS, HIPCC_FLAGS)).encode())
+    h.update(repr((HIP_TUS, HIPCC_FLAGS)).encode())
     return h.hexdigest()[:16]
 
 
@@ -69,7 +93,7 @@ def build_hip(force=False, verbose=False):
     vdir = os.environ.get("BNFLAC_VARIANT_DIR")
     libdir = vdir or LIB
     out = os.path.join(libdir, "libbnflac.so")
-    if force or _stale(out, HIP_SOURCES + HIP_HEADERS):
+    if force or _stale(out, hip_inputs()):
         os.makedirs(libdir, exist_ok=True)
         objdir = os.path.join(vdir, "build") if vdir else os.path.join(PKG, "build")
         os.makedirs(objdir, exist_ok=True)
@@ -77,18 +101,15 @@ def build_hip(force=False, verbose=False):
         if vdir:
             base += os.environ.get("BNFLAC_EXTRA_CFLAGS", "").split()
         jobs, objs = [], []
-        # development shortcut: BNFLAC_DEV_TUS="1,3" recompiles only those kernel TUs and
-        # reuses the other objects as they are (never set for a real build)
+        # development shortcut: BNFLAC_DEV_TUS="bnflac_kernels_tu1,bnflac_sys" recompiles only
+        # those kernel objects (and the host .cpp files) and reuses the others as they are
+        # (never set for a real build)
         dev = os.environ.get("BNFLAC_DEV_TUS")
-        only = {int(x) for x in dev.split(",")} if dev else None
-        for tu in KERNEL_TUS:
-            o = os.path.join(objdir, f"bnflac_kernels_tu{tu}.o")
-            if only is None or tu in only or not os.path.exists(o):
-                jobs.append(base + [f"-DBNF_TU={tu}", "-c", HIP_SOURCES[0], "-o", o])
-            objs.append(o)
-        for src in HIP_SOURCES[1:]:
-            o = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
-            jobs.append(base + ["-c", src, "-o", o])
+        only = set(dev.split(",")) if dev else None
+        for src, defs, name in HIP_TUS:
+            o = os.path.join(objdir, name + ".o")
+            if only is None or name in only or src.endswith(".cpp") or not os.path.exists(o):
+                jobs.append(base + defs + ["-c", os.path.join(CSRC, src), "-o", o])
             objs.append(o)
         procs = []
         for cmd in jobs:

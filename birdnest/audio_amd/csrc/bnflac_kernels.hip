@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "bnflac_device.h"
+#include "bnflac_launch.h" /* the `ablate` word (BNF_ABLATE_*, BNF_MODE_*) and every cross-TU declaration */
 
 #define DEV __device__ __forceinline__
 
@@ -104,28 +105,6 @@ typedef __attribute__((address_space(1))) const void gvoid;
  * lgkmcnt -- every later LDS wait would then wait for the HBM write) */
 DEV void gst128(uint64_t addr, u32x4 v) { *(__attribute__((address_space(1))) u32x4 *)addr = v; }
 
-/* Mode bits carried in the kernels' `ablate` word (set by the launchers, never a timing
- * ablation).  Mode bit: the lane kernel decodes only the frames k_decode_sys handed back (BNF_FL_WAVE_REDO). */
-#define BNF_MODE_WREDO 0x4000u
-/* Mode bit: k_decode_sw ran before the other lane kernels (they take its SW frames only when
- * it handed them back).  Host ablation bit BNF_ABLATE_NO_SW: do not launch it. */
-#define BNF_MODE_SW 0x8000u
-#define BNF_ABLATE_NO_SW 0x10000u
-/* Mode bit: k_decode_list -- the frames of a device list (k_decode_sys's hand-backs), every
- * class, decoded by this instance (no class split, stereo fast-path frames included). */
-#define BNF_MODE_LIST 0x20000u
-/* Mode bit: k_decode_seg -- the W = 32 instance also takes the W16 class's blocks. */
-#define BNF_MODE_SEG 0x80000000u
-/* Mode bits of the W = 8 instance when its two jobs run as two launches (bnf_launch_decode):
- * NOST -- the narrow non-stereo frames only (the decode order's class 1; beside k_decode_st,
- * so it never reads a stereo frame's hand-back bit); STREDO -- only the stereo frames
- * k_decode_st handed back (class 0; after it). */
-#define BNF_MODE_NOST 0x40000u
-#define BNF_MODE_STREDO 0x80000u
-#define BNF_ABLATE_NO_W8SPLIT 0x100000u /* host A/B bit: the W = 8 instance as one launch */
-/* A/B bit (exact): k_decode_st keeps no running CRC-16 of channel 1 in its chunk loop; the tail
- * reads channel 1 again from k_parse's prefix on */
-#define BNF_ABLATE_NO_STFOLD 0x40u
 
 /* ----------------------------------------------------------------- bit reader */
 #define RING_MAX 16       /* 16-byte slots per lane (k_parse and k_decode_st use 8) */
@@ -1047,7 +1026,6 @@ DEV void pk_next_word(BR &b) { b.nx = *(const lds_u32 *)((const __attribute__((a
  * br_skip over an escaped partition, the generic readers of the rare paths, candidate frames
  * of arbitrary bytes) the whole wave takes br_refill, which catches up any distance.
  * BNF_ABLATE_PARSE_BLKREFILL: br_refill always (the exact A/B switch). */
-#define BNF_ABLATE_PARSE_BLKREFILL 0x800000u
 DEV void pk_refill(BR &b, uint32_t ablate) {
     const uint32_t cg = (b.wi >> 2) & ~3u; /* first block of the cursor's group */
     /* iend and cg are multiples of 4: in the ring iff iend is cg + 4 or cg + 8 */
@@ -1132,14 +1110,14 @@ DEV uint32_t skip_residual_t(BR &b, const SubHdr &h, uint32_t bs, uint64_t limit
     pk_resync(b, lane);
     while (any_lane(rem != 0u || p < parts)) {
         if (BULK) {
-            if (__builtin_amdgcn_readfirstlane(since) >= 12u && !(ablate & 32u)) { /* every 12-14 steps */
+            if (__builtin_amdgcn_readfirstlane(since) >= 12u && !(ablate & BNF_ABLATE_NO_WALK_REFILL)) { /* every 12-14 steps */
                 if (CP) crcp_hook(cp, b, lane, b.wi >> 4); /* the lines loaded, before the refill overwrites them */
                 pk_refill(b, ablate);
                 pk_resync(b, lane);
                 since = 0;
             }
             since += 2u;
-        } else if ((__builtin_amdgcn_readfirstlane(since++) & 7u) == 0u && !(ablate & 32u)) { /* every 16 steps */
+        } else if ((__builtin_amdgcn_readfirstlane(since++) & 7u) == 0u && !(ablate & BNF_ABLATE_NO_WALK_REFILL)) { /* every 16 steps */
             if (CP) crcp_hook(cp, b, lane, b.wi >> 4);
             pk_refill(b, ablate);
             pk_resync(b, lane);
@@ -1754,7 +1732,7 @@ DEV void parse_frame(const uint32_t *__restrict__ words, uint64_t nbytes, const 
     crcp_init(cp);
     uint32_t st = parse_header(b, fbit, limit, sp, fi);
     if (st == BNF_ST_ERROR && br_pos(b) > limit) st = BNF_ST_TRUNC;
-    if (CPM && crcp != nullptr && st == BNF_ST_OK && fi.channels == 2u && !(ablate & 16u)) {
+    if (CPM && crcp != nullptr && st == BNF_ST_OK && fi.channels == 2u && !(ablate & BNF_ABLATE_NO_WALK)) {
         /* the frame's first line, its bytes below frame_off cleared (L2-warm: the ring's
          * refill just read it).  Only the 16-byte blocks that start inside the 16-byte-rounded
          * buffer are read (st_crc16_ok's tail rule), the rest taken as zeros: a line the buffer
@@ -1794,7 +1772,7 @@ DEV void parse_frame(const uint32_t *__restrict__ words, uint64_t nbytes, const 
                 raw = raw || (x & 0x7Eu) < 4u;
                 break;
             }
-            if (ablate & 16u) {
+            if (ablate & BNF_ABLATE_NO_WALK) {
 #pragma unroll
                 for (int c = 0; c < 8; c++) ss[c] = (uint32_t)c == ch + 1 ? here : ss[c];
                 continue;
@@ -2616,7 +2594,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
         bool w = false;
         if (have && info[f].status == BNF_ST_OK) {
             const uint32_t fl = info[f].flags;
-            if ((fl & BNF_FL_ST) && !(ablate & 0x400u)) w = !(ablate & BNF_MODE_NOST) && (fl & BNF_FL_REDO) != 0;
+            if ((fl & BNF_FL_ST) && !(ablate & BNF_ABLATE_NO_ST)) w = !(ablate & BNF_MODE_NOST) && (fl & BNF_FL_REDO) != 0;
             else w = !(ablate & BNF_MODE_STREDO) && !(fl & (BNF_FL_W16 | BNF_FL_W32));
         }
         if (!__any(w)) return;
@@ -2626,7 +2604,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
      * those are decoded by the W = 8 instance, which runs after k_decode_st on its stream.
      * The W = 16 and 32 instances run beside them on a second stream and never look at
      * ST frames (the ST bit is k_parse's and does not change; REDO may be being set). */
-    const bool st_frame = have && (fi.flags & BNF_FL_ST) && !(ablate & 0x400u) && !lst;
+    const bool st_frame = have && (fi.flags & BNF_FL_ST) && !(ablate & BNF_ABLATE_NO_ST) && !lst;
     if (st_frame && (MAXW != 8 || (ablate & BNF_MODE_NOST) || !(fi.flags & BNF_FL_REDO))) have = false;
     if (MAXW == 8 && (ablate & BNF_MODE_STREDO) && !st_frame) have = false;
     if (have && sw_on && (fi.flags & BNF_FL_SW) && !(fi.flags & BNF_FL_REDO)) have = false;
@@ -2692,7 +2670,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
     const uint32_t fbs = fok ? f_bs[fl] : 0u, fch = have ? fi.channels : 0u, fas = fok ? f_as[fl] : 0u;
     const uint64_t fos = fok ? f_out[fl] : 0u;
     lds_sync(); /* the ring's first DMA may overwrite the tables only after these reads */
-    const bool wide_fmt = fmt == BNF_OUT_FILEREADER && sp.bps == 24u && !(ablate & 0x2000u);
+    const bool wide_fmt = fmt == BNF_OUT_FILEREADER && sp.bps == 24u && !(ablate & BNF_ABLATE_NO_WIDE24);
     if (wide_fmt && fl < fpb && ch == 0) { /* pack_wide24's frame table (row buffer spare columns) */
         uint32_t *t = wide_tbl(lds, fl);
         const uint64_t ob = fos * sp.channels * 3u;
@@ -2705,7 +2683,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
     /* ---- subframe setup */
     BR b;
     br_init(b, words, nbytes, (lds_u32 *)ring, lane, RD);
-    b.stats = (ablate & 0x100u) != 0;
+    b.stats = (ablate & BNF_ABLATE_STATS) != 0;
     STAT(b.stats, 5);
     const bool tmon = b.stats;
     const uint64_t t_start = tnow(tmon);
@@ -2802,7 +2780,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
         br_wait1(b, vq); /* the lines fetched after the last entropy phase have landed */
         /* full chunks past the warm-up: fused decode + restore; the warm-up chunk and a
          * frame's last partial chunk: residuals into the rows, then the restore */
-        const bool fused = nvalid == CHK && n0 >= pd.order && !(ablate & 0x80Cu);
+        const bool fused = nvalid == CHK && n0 >= pd.order && !(ablate & (BNF_ABLATE_NO_FUSED | BNF_ABLATE_NO_RICE | BNF_ABLATE_NO_RESTORE));
         if (fused) {
             STAT(b.stats, 0);
             if (MAXW == 16 && ntap_lo) fused_chunk<CHK, MAXW, NTAP_LO>(b, rs, row, c, x, xt, pd, limit, trunc);
@@ -2810,7 +2788,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
         } else if (nvalid) {
             STAT(b.stats, 1);
             const uint32_t i0 = (n0 < pd.order) ? min(pd.order - n0, nvalid) : 0u;
-            if (ablate & 8u) {
+            if (ablate & BNF_ABLATE_NO_RICE) {
                 for (uint32_t i = i0; i < nvalid; i++) row[i * RP] = (int32_t)i;
             } else {
                 for (uint32_t i = i0; i < nvalid; i++) row[i * RP] = rice_fused(b, rs, limit, trunc, nullptr);
@@ -2822,7 +2800,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
             STAT(b.stats && want, 4);
             br_issue(b, want);
         }
-        if (!fused && nvalid && !(ablate & 4u)) {
+        if (!fused && nvalid && !(ablate & BNF_ABLATE_NO_RESTORE)) {
             if (MAXW == 16 && ntap_lo) restore_chunk<CHK, MAXW, NTAP_LO>(row, c, x, xt, pd, n0, nvalid);
             else restore_chunk<CHK, MAXW, MAXW>(row, c, x, xt, pd, n0, nvalid);
         }
@@ -2831,7 +2809,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
         tm_dec += tb - ta;
         tm_ref += tc - tb;
         uint32_t pk = 0;
-        switch ((ablate & 2u) ? -1 : fmt) {
+        switch ((ablate & BNF_ABLATE_NO_STORE) ? -1 : fmt) {
         case -1:
             break;
         case BNF_OUT_PLANAR32:
@@ -2942,7 +2920,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
         const uint32_t nl = fch;
         const uint64_t per = (len + nl - 1) / nl;
         const uint64_t s0 = f_off + min(len, per * ch), s1 = f_off + min(len, per * (ch + 1));
-        if (!(ablate & 1u)) {
+        if (!(ablate & BNF_ABLATE_NO_CRC16)) {
             part = crc16_range((const uint8_t *)words, s0, s1, T);
             part = crc16_shift(part, f_off + len - s1);
         }
@@ -2950,7 +2928,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
     /* xor-reduce within each frame's lane group */
     uint32_t acc = part;
     for (uint32_t o = 1; o < chn_lanes; o <<= 1) acc ^= __shfl_xor(acc, o);
-    if ((ablate & 1u) && last && t_status == BNF_ST_OK) acc = t_crc_read;
+    if ((ablate & BNF_ABLATE_NO_CRC16) && last && t_status == BNF_ST_OK) acc = t_crc_read;
     if (last) {
         bnf_frame_info fo = info[f];
         fo.status = t_status;
@@ -4453,7 +4431,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
     lds_u32 *ring0 = (lds_u32 *)ring, *ring1 = (lds_u32 *)ring + ST_RD * RING_LANE_DW;
     br_init(z0.b, words, nbytes, ring0, lane, ST_RD);
     br_init(z1.b, words, nbytes, ring1, lane, ST_RD);
-    z0.b.stats = z1.b.stats = (ablate & 0x100u) != 0;
+    z0.b.stats = z1.b.stats = (ablate & BNF_ABLATE_STATS) != 0;
     STAT(z0.b.stats, 5);
     const bool tmon = z0.b.stats;
     const uint64_t t_start = tnow(tmon);
@@ -4483,12 +4461,12 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
     uint32_t trunc = 0;
     /* channel 1's running CRC-16 (StFold), folded at the chunk's refill points (st_fold_point);
      * the wave-uniform switch BNF_ABLATE_NO_STFOLD leaves the tail its re-read from the prefix */
-    const bool fold_on = crcp != nullptr && !(ablate & (BNF_ABLATE_NO_STFOLD | 1u));
+    const bool fold_on = crcp != nullptr && !(ablate & (BNF_ABLATE_NO_STFOLD | BNF_ABLATE_NO_CRC16));
     StFold fold;
     st_fold_start(fold, z1.b, words, crcp, f, ok ? fi.frame_off : 0u, fold_on && ok);
     wait_vm(); /* setup loads done: the store count starts from zero */
     uint32_t nst = 0; /* vector-memory ops (PCM stores) issued by this wave since the last refill's DMAs */
-    const bool sto = !(ablate & 2u);
+    const bool sto = !(ablate & BNF_ABLATE_NO_STORE);
     /* refill: wait for the previous refill's DMAs (every store since stays in flight), then
      * issue the next blocks; stores issued after it are younger.  (Round 5: waiting for the
      * refill before last instead, with the landing check covering the newest group, measured
@@ -4507,7 +4485,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         const uint64_t ta = tnow(tmon);
         const uint32_t n0 = kc * ST2_CHK;
         const bool valid = ok && n0 < bs;
-        bool fast = valid && n0 >= 8u && n0 + ST2_CHK <= bs && !(ablate & 12u);
+        bool fast = valid && n0 >= 8u && n0 + ST2_CHK <= bs && !(ablate & (BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE));
         if (fast) { /* partition headers at the chunk boundary (aligned partitions) */
             if (z0.left == 0 && z0.parts_left()) st_partition(z0, bs);
             if (z1.left == 0 && z1.parts_left()) st_partition(z1, bs);
@@ -4602,7 +4580,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
             uint64_t run = (valid && sto) ? (uint64_t)(uintptr_t)(dst + (uint64_t)n0 * 4u) : 0ull;
             /* timing ablation 0x10000000: the same stores into one 64 KB window per XCD (an
              * L2-resident footprint: the HBM write traffic without the instructions); wrong PCM */
-            if ((ablate & 0x10000000u) && run && out_bytes >= (1u << 20)) /* the window needs 513 KB */
+            if ((ablate & BNF_ABLATE_HOT_WINDOW) && run && out_bytes >= (1u << 20)) /* the window needs 513 KB */
                 run = (uint64_t)(uintptr_t)(out + (uint64_t)(blockIdx.x & 7u) * 65536u + lane * 1024u + ((n0 * 4u) & 1023u));
             const uint32_t rlo = (uint32_t)run, rhi = (uint32_t)(run >> 32);
             const uint32_t fr = lane & 31u, ul = lane & 7u;
@@ -4672,7 +4650,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
      * and st_crc16_run continues it over the frame's last lines only, or, for a lane whose
      * fold stopped early, from wherever it stopped. */
     uint32_t crc = crc_read;
-    if (ok && !(ablate & 1u)) {
+    if (ok && !(ablate & BNF_ABLATE_NO_CRC16)) {
         bool used;
 #ifdef BNFLAC_CRC_FOLD_CHECK
         /* check build: both verdicts, and the lanes whose two final remainders differ */
@@ -5072,7 +5050,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
     uint8_t *dst = out + os * stride;
     /* timing ablation 0x10000000: every wave stores into one 64 KB window (same store
      * instructions, an L2-resident footprint); output is wrong */
-    const bool hot = (ablate & 0x10000000u) != 0 && out_bytes >= (1u << 20); /* the window needs 513 KB */
+    const bool hot = (ablate & BNF_ABLATE_HOT_WINDOW) != 0 && out_bytes >= (1u << 20); /* the window needs 513 KB */
     if (hot) dst = out + (uint64_t)(blockIdx.x & 7u) * 65536u + lane * 1024u;
     const bool al = (((uintptr_t)dst) & 15u) == 0 && (FMT != BNF_OUT_PLANAR32 || (bs & 3u) == 0);
     const bool all_al = !any_lane(ok && !al); /* every run of the wave takes the 16-byte stores */
@@ -5101,11 +5079,11 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
     for (int o = 32; o > 0; o >>= 1) mybs = max(mybs, (uint32_t)__shfl_xor(mybs, o));
     const uint32_t nchunks = (mybs + ST_CHK - 1) / ST_CHK;
     uint32_t trunc = 0;
-    const bool sto = !(ablate & 2u);
+    const bool sto = !(ablate & BNF_ABLATE_NO_STORE);
     /* FILEREADER runs that start on a 64-byte line: the fused chunks flush whole lines
      * (sw_line_flush); the slots sit past the two rings (the 4 KB staging tile).
      * Ablation bit 0x20000000 (exact): per-lane 16-byte stores instead */
-    const bool line = FMT == BNF_OUT_FILEREADER && sto && !hot && all_al && !(ablate & 0x20000000u) &&
+    const bool line = FMT == BNF_OUT_FILEREADER && sto && !hot && all_al && !(ablate & BNF_ABLATE_SW_NO_LINE) &&
                       !any_lane(ok && (((uintptr_t)dst) & 63u) != 0);
     lds_u32x4 *stg = (lds_u32x4 *)((lds_u32 *)ring + 2u * ST_RD * RING_LANE_DW);
     static_assert(sizeof(ring) >= (2 * ST_RD * RING_LANE_DW + 1024) * 4, "the flush's 4 KB staging tile lies past the two rings");
@@ -5120,7 +5098,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
     for (uint32_t kc = 0; kc < nchunks; kc++) {
         const uint32_t n0 = kc * ST_CHK;
         const bool valid = ok && n0 < bs;
-        bool fast = valid && n0 >= 16u && n0 + ST_CHK <= bs && !(ablate & 12u);
+        bool fast = valid && n0 >= 16u && n0 + ST_CHK <= bs && !(ablate & (BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE));
         if (fast) { /* partition headers at the chunk boundary (aligned partitions) */
             if (z0.left == 0 && z0.pidx < z0.nparts) st_partition(z0);
             if (z1.left == 0 && z1.pidx < z1.nparts) st_partition(z1);
@@ -5248,7 +5226,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
     }
     uint32_t crc = crc_read;
     /* the table-free zero test over frame + footer (round 6: 9.40 -> 9.23 ms on C3, same box) */
-    if (ok && !(ablate & 1u) && !st_crc16_frame((const uint8_t *)words, crcp, f, fi.frame_off, end_byte + 2u)) ok = false;
+    if (ok && !(ablate & BNF_ABLATE_NO_CRC16) && !st_crc16_frame((const uint8_t *)words, crcp, f, fi.frame_off, end_byte + 2u)) ok = false;
     if (ok && crc != crc_read) ok = false;
     if (ok) {
         info[f].resume_bit = resume;
@@ -5263,40 +5241,18 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
 #endif /* BNF_TU == 3 || BNF_TU == 4 || BNF_TU == 7 */
 
 /* ------------------------------------------------------------- host launchers */
-/* The library is built from this file three times (BNF_TU 0: sync scan + k_parse + shared
- * launchers, 1: k_decode<8>, 2: k_decode<32>), so the instances compile in parallel.  Each
- * TU is its own code object: the __constant__ tables are uploaded into every one. */
-/* mode switches are read by launching threads while a test or tool may set them: atomics */
-static std::atomic<uint32_t> g_ablate{0xFFFFFFFFu};
-static uint32_t ablate_flags() {
-    uint32_t v = g_ablate.load(std::memory_order_relaxed);
-    if (v == 0xFFFFFFFFu) {
-        const char *e = getenv("BNFLAC_ABLATE"); /* timing experiments only: results are wrong */
-        v = e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
-        g_ablate.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-static hipError_t upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
+/* The library is built from this file once per BNF_TU (build.py HIP_TUS), so the instances
+ * compile in parallel.  Each TU is its own code object with its own __constant__ tables and
+ * g_stats: the two functions below act on this TU's copy, and each TU publishes them as its
+ * bnf_tu_ops entry (bnflac_launch.h), which TU 0 loops over. */
+static hipError_t tu_upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc8_tab), crc8, 256);
     if (e != hipSuccess) return e;
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc16_tab), crc16x8, 8 * 256 * sizeof(uint16_t));
     if (e != hipSuccess) return e;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_crc16_xpow), xpow, 40 * sizeof(uint16_t));
 }
-
-#define TU_FN(name) TU_FN2(name, BNF_TU)
-#define TU_FN2(name, n) TU_FN3(name, n)
-#define TU_FN3(name, n) name##_tu##n
-#if BNF_TU == 1 || BNF_TU == 2 || BNF_TU == 5
-#define DEC_W (BNF_TU == 1 ? 8 : (BNF_TU == 5 ? 16 : 32))
-#define DEC_RD 8 /* ring slots (16 for k_decode<32> measured: LDS then caps it at 6 waves per CU) */
-extern "C" {
-hipError_t TU_FN(bnf_upload_tables)(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
-    return upload_tables(crc8, crc16x8, xpow);
-}
-void TU_FN(bnf_set_ablate)(uint32_t v) { g_ablate.store(v, std::memory_order_relaxed); }
-hipError_t TU_FN(bnf_stats)(uint64_t *out16, int reset) {
+static hipError_t tu_stats(uint64_t *out16, int reset) { /* adds this TU's g_stats to out16 */
     uint64_t v[16];
     hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_stats), sizeof v);
     if (e != hipSuccess) return e;
@@ -5307,6 +5263,26 @@ hipError_t TU_FN(bnf_stats)(uint64_t *out16, int reset) {
     }
     return e;
 }
+
+/* what this TU holds, as the suffix of its launcher and of its bnf_tu_ops entry */
+#if BNF_TU == 1
+#define TU_FN(name) name##_w8
+#elif BNF_TU == 2
+#define TU_FN(name) name##_w32
+#elif BNF_TU == 5
+#define TU_FN(name) name##_w16
+#elif BNF_TU == 3
+#define TU_FN(name) name##_st_fd
+#elif BNF_TU == 4
+#define TU_FN(name) name##_st_any
+#elif BNF_TU == 7
+#define TU_FN(name) name##_sw
+#endif
+#if BNF_TU == 1 || BNF_TU == 2 || BNF_TU == 5
+#define DEC_W (BNF_TU == 1 ? 8 : (BNF_TU == 5 ? 16 : 32))
+#define DEC_RD 8 /* ring slots (16 for k_decode<32> measured: LDS then caps it at 6 waves per CU) */
+bnf_tu_ops TU_FN(bnf_ops_decode) = {tu_upload_tables, tu_stats};
+extern "C" {
 /* seg: k_order's bucket ends (W = 16 / 32 only, with perm): blocks outside the class leave first */
 hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                     uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
@@ -5315,28 +5291,28 @@ hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint
     const uint32_t nb = (nframes + fpb - 1) / fpb;
     if (!perm || (DEC_W == 8 && !(mode & (BNF_MODE_NOST | BNF_MODE_STREDO)))) seg = nullptr;
     hipLaunchKernelGGL((k_decode<DEC_W, 32, DEC_RD>), dim3(nb), dim3(DEC_LANES), 0, s, words, nbytes, nframes, sp, chn_lanes,
-                       fmt, out, out_bytes, info, perm, ablate_flags() | mode, seg);
+                       fmt, out, out_bytes, info, perm, (bnf_ablate_flags() & BNF_ABLATE_K_DECODE) | (mode & BNF_MODE_K_DECODE), seg);
     return hipGetLastError();
 }
 #if BNF_TU == 2
 /* k_decode_sys's hand-back list (W = 32: every order); nframes bounds the list */
-hipError_t bnf_launch_decode_list_tu2(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
+hipError_t bnf_launch_decode_list(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                       uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
                                       const uint32_t *list, uint32_t mode, hipStream_t s) {
     const uint32_t fpb = DEC_LANES / chn_lanes;
     const uint32_t nb = std::min<uint32_t>((nframes + fpb - 1) / fpb, 512u);
     hipLaunchKernelGGL((k_decode_list<DEC_W, 32, DEC_RD>), dim3(std::max(nb, 1u)), dim3(DEC_LANES), 0, s, words, nbytes, sp,
-                       chn_lanes, fmt, out, out_bytes, info, list, ablate_flags() | mode);
+                       chn_lanes, fmt, out, out_bytes, info, list, (bnf_ablate_flags() & BNF_ABLATE_K_DECODE) | (mode & BNF_MODE_K_DECODE));
     return hipGetLastError();
 }
 /* the W16 + W32 segment of the decode order (k_decode_seg; perm and seg required) */
-hipError_t bnf_launch_decode_seg_tu2(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
+hipError_t bnf_launch_decode_seg(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                      uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
                                      const uint32_t *perm, uint32_t mode, const uint32_t *seg, hipStream_t s) {
     const uint32_t fpb = DEC_LANES / chn_lanes;
     const uint32_t nb = std::min<uint32_t>((nframes + fpb - 1) / fpb, 512u);
     hipLaunchKernelGGL((k_decode_seg<DEC_W, 32, DEC_RD>), dim3(std::max(nb, 1u)), dim3(DEC_LANES), 0, s, words, nbytes,
-                       nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, ablate_flags() | mode | BNF_MODE_SEG, seg);
+                       nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, (bnf_ablate_flags() & BNF_ABLATE_K_DECODE) | (mode & BNF_MODE_K_DECODE) | BNF_MODE_SEG, seg);
     return hipGetLastError();
 }
 #endif
@@ -5345,29 +5321,15 @@ hipError_t bnf_launch_decode_seg_tu2(const uint32_t *words, uint64_t nbytes, uin
 
 #if BNF_TU == 3 || BNF_TU == 4
 /* TU 3: k_decode_st<FLACDECODER>; TU 4: the other layouts */
+bnf_tu_ops TU_FN(bnf_ops_decode) = {tu_upload_tables, tu_stats};
 extern "C" {
-hipError_t TU_FN(bnf_upload_tables)(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
-    return upload_tables(crc8, crc16x8, xpow);
-}
-void TU_FN(bnf_set_ablate)(uint32_t v) { g_ablate.store(v, std::memory_order_relaxed); }
-hipError_t TU_FN(bnf_stats)(uint64_t *out16, int reset) {
-    uint64_t v[16];
-    hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_stats), sizeof v);
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < 16; i++) out16[i] += v[i];
-    if (reset) {
-        static const uint64_t z[16] = {0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_stats), z, sizeof z);
-    }
-    return e;
-}
 /* stereo fast path; launched before k_decode<8> (it hands frames back to it) */
 hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                     uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
                                     const uint32_t *perm, uint32_t mode, const uint32_t *crcp, hipStream_t s) {
     const dim3 grid((nframes + 63) / 64);
-    const uint32_t ab = ablate_flags() | mode;
-    if (ab & 0x400u) return hipSuccess; /* timing ablation: everything to k_decode<8> */
+    const uint32_t ab = (bnf_ablate_flags() & BNF_ABLATE_K_DECODE_ST) | (mode & BNF_MODE_K_DECODE_ST);
+    if (ab & BNF_ABLATE_NO_ST) return hipSuccess; /* everything to k_decode<8> */
 #if BNF_TU == 3
     (void)fmt;
     hipLaunchKernelGGL(k_decode_st<BNF_OUT_FLACDECODER>, grid, dim3(64), 0, s, words, nbytes, nframes, sp, chn_lanes, out, out_bytes, info, perm, ab, crcp);
@@ -5390,28 +5352,14 @@ hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint
 #endif
 
 #if BNF_TU == 7
+bnf_tu_ops TU_FN(bnf_ops_decode) = {tu_upload_tables, tu_stats};
 extern "C" {
-hipError_t TU_FN(bnf_upload_tables)(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
-    return upload_tables(crc8, crc16x8, xpow);
-}
-void TU_FN(bnf_set_ablate)(uint32_t v) { g_ablate.store(v, std::memory_order_relaxed); }
-hipError_t TU_FN(bnf_stats)(uint64_t *out16, int reset) {
-    uint64_t v[16];
-    hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_stats), sizeof v);
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < 16; i++) out16[i] += v[i];
-    if (reset) {
-        static const uint64_t z[16] = {0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_stats), z, sizeof z);
-    }
-    return e;
-}
 /* stereo frames above 16 bits; launched before k_decode<8>/<16>/<32> (it hands frames back to k_decode<16>) */
-hipError_t bnf_launch_decode_sw_tu7(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
+hipError_t bnf_launch_decode_sw(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                     uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
                                     const uint32_t *perm, uint32_t mode, const uint32_t *crcp, hipStream_t s) {
     const dim3 grid((nframes + 63) / 64);
-    const uint32_t ab = ablate_flags() | mode;
+    const uint32_t ab = (bnf_ablate_flags() & BNF_ABLATE_K_DECODE_SW) | (mode & BNF_MODE_K_DECODE_SW);
     switch (fmt) {
     case BNF_OUT_PLANAR32:
         hipLaunchKernelGGL(k_decode_sw<BNF_OUT_PLANAR32>, grid, dim3(64), 0, s, words, nbytes, nframes, sp, chn_lanes, out, out_bytes, info, perm, ab, crcp);
@@ -5430,56 +5378,26 @@ hipError_t bnf_launch_decode_sw_tu7(const uint32_t *words, uint64_t nbytes, uint
 #endif
 
 #if BNF_TU == 0
+/* mode switches are read by launching threads while a test or tool may set them: atomics */
+static std::atomic<uint32_t> g_ablate{0xFFFFFFFFu};
+/* every kernel TU but this one (its tables are uploaded first, its g_stats are not reported) */
+static const bnf_tu_ops *const g_tus[] = {&bnf_ops_decode_w8,  &bnf_ops_decode_w32, &bnf_ops_decode_st_fd, &bnf_ops_decode_st_any,
+                                          &bnf_ops_decode_w16, &bnf_ops_decode_sw,  &bnf_ops_decode_sys};
 extern "C" {
-hipError_t bnf_upload_tables_tu3(const uint8_t *, const uint16_t *, const uint16_t *);
-hipError_t bnf_upload_tables_tu4(const uint8_t *, const uint16_t *, const uint16_t *);
-void bnf_set_ablate_tu3(uint32_t);
-void bnf_set_ablate_tu4(uint32_t);
-hipError_t bnf_stats_tu3(uint64_t *, int);
-hipError_t bnf_stats_tu4(uint64_t *, int);
-hipError_t bnf_launch_decode_tu3(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                 uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
-hipError_t bnf_launch_decode_tu4(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                 uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
-hipError_t bnf_launch_decode_sw_tu7(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                    uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
-hipError_t bnf_upload_tables_tu5(const uint8_t *, const uint16_t *, const uint16_t *);
-void bnf_set_ablate_tu5(uint32_t);
-hipError_t bnf_stats_tu5(uint64_t *, int);
-hipError_t bnf_launch_decode_tu5(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                 uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
-hipError_t bnf_upload_tables_tu1(const uint8_t *, const uint16_t *, const uint16_t *);
-hipError_t bnf_upload_tables_tu2(const uint8_t *, const uint16_t *, const uint16_t *);
-hipError_t bnf_upload_tables_tu7(const uint8_t *, const uint16_t *, const uint16_t *);
-void bnf_set_ablate_tu7(uint32_t);
-hipError_t bnf_stats_tu7(uint64_t *, int);
-hipError_t bnf_upload_tables_tu8(const uint8_t *, const uint16_t *, const uint16_t *);
-hipError_t bnf_stats_tu8(uint64_t *, int);
-void bnf_set_ablate_tu8(uint32_t);
-hipError_t bnf_launch_decode_sys_tu8(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                     uint64_t, bnf_frame_info *, const uint32_t *, uint32_t *, uint32_t, hipStream_t);
-hipError_t bnf_launch_decode_list_tu2(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                      uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, hipStream_t);
-hipError_t bnf_launch_decode_seg_tu2(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                     uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
-void bnf_set_ablate_tu1(uint32_t);
-void bnf_set_ablate_tu2(uint32_t);
-hipError_t bnf_stats_tu1(uint64_t *, int);
-hipError_t bnf_stats_tu2(uint64_t *, int);
-hipError_t bnf_launch_decode_tu1(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                 uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
-hipError_t bnf_launch_decode_tu2(const uint32_t *, uint64_t, uint32_t, bnf_stream_params, uint32_t, int, uint8_t *,
-                                 uint64_t, bnf_frame_info *, const uint32_t *, uint32_t, const uint32_t *, hipStream_t);
+uint32_t bnf_ablate_flags(void) {
+    uint32_t v = g_ablate.load(std::memory_order_relaxed);
+    if (v == 0xFFFFFFFFu) {
+        const char *e = getenv("BNFLAC_ABLATE"); /* timing experiments only: results are wrong */
+        v = e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
+        g_ablate.store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
 
 hipError_t bnf_upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
-    hipError_t e = upload_tables(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu1(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu2(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu3(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu4(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu5(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu7(crc8, crc16x8, xpow);
-    if (e == hipSuccess) e = bnf_upload_tables_tu8(crc8, crc16x8, xpow);
+    hipError_t e = tu_upload_tables(crc8, crc16x8, xpow);
+    for (const bnf_tu_ops *tu : g_tus)
+        if (e == hipSuccess) e = tu->upload_tables(crc8, crc16x8, xpow);
     return e;
 }
 
@@ -5499,26 +5417,14 @@ uint32_t bnf_scan_blocks(uint64_t n) {
     return (uint32_t)((n + per_block - 1) / per_block);
 }
 
-void bnf_set_ablate(uint32_t v) {
-    g_ablate.store(v, std::memory_order_relaxed);
-    bnf_set_ablate_tu1(v);
-    bnf_set_ablate_tu2(v);
-    bnf_set_ablate_tu3(v);
-    bnf_set_ablate_tu4(v);
-    bnf_set_ablate_tu5(v);
-    bnf_set_ablate_tu7(v);
-    bnf_set_ablate_tu8(v);
-}
+void bnf_set_ablate(uint32_t v) { g_ablate.store(v, std::memory_order_relaxed); }
 
 hipError_t bnf_stats(uint64_t *out16, int reset) {
     for (int i = 0; i < 16; i++) out16[i] = 0;
-    hipError_t e = bnf_stats_tu1(out16, reset);
-    if (e == hipSuccess) e = bnf_stats_tu2(out16, reset);
-    if (e == hipSuccess) e = bnf_stats_tu3(out16, reset);
-    if (e == hipSuccess) e = bnf_stats_tu5(out16, reset);
-    if (e == hipSuccess) e = bnf_stats_tu7(out16, reset);
-    if (e == hipSuccess) e = bnf_stats_tu8(out16, reset);
-    return e == hipSuccess ? bnf_stats_tu4(out16, reset) : e;
+    hipError_t e = hipSuccess;
+    for (const bnf_tu_ops *tu : g_tus)
+        if (e == hipSuccess) e = tu->stats(out16, reset);
+    return e;
 }
 
 /* words: 16-byte aligned; the allocation must cover round_up(nbytes, 16) bytes. */
@@ -5794,13 +5700,13 @@ hipError_t bnf_launch_parse(const uint32_t *words, uint64_t nbytes, const uint64
     const dim3 g((nframes + 63) / 64);
     if (cm == 2)
         hipLaunchKernelGGL(k_parse<2>, g, dim3(64), 0, s, words, nbytes, frame_offs, nframes, sp, out_sample_in,
-                           base_sample, info, ablate_flags(), perm, crcp);
+                           base_sample, info, bnf_ablate_flags() & BNF_ABLATE_K_PARSE, perm, crcp);
     else if (cm == 1)
         hipLaunchKernelGGL(k_parse<1>, g, dim3(64), 0, s, words, nbytes, frame_offs, nframes, sp, out_sample_in,
-                           base_sample, info, ablate_flags(), perm, crcp);
+                           base_sample, info, bnf_ablate_flags() & BNF_ABLATE_K_PARSE, perm, crcp);
     else
         hipLaunchKernelGGL(k_parse<0>, g, dim3(64), 0, s, words, nbytes, frame_offs, nframes, sp, out_sample_in,
-                           base_sample, info, ablate_flags(), perm, nullptr);
+                           base_sample, info, bnf_ablate_flags() & BNF_ABLATE_K_PARSE, perm, nullptr);
     return hipGetLastError();
 }
 
@@ -5826,9 +5732,9 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
         hipError_t e = hipMemsetAsync(list, 0, 16, s);
         if (e == hipSuccess) e = launch_order<0>(info, nullptr, 0, nullptr, nframes, order, &perm, s);
         if (e == hipSuccess)
-            e = bnf_launch_decode_sys_tu8(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, list, mode, s);
+            e = bnf_launch_decode_sys(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, list, mode, s);
         if (e == hipSuccess)
-            e = bnf_launch_decode_list_tu2(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, list, mode, s);
+            e = bnf_launch_decode_list(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, list, mode, s);
         return e;
     }
     /* the class segments of the decode order (bucket ends), for the W16 / W32 grids */
@@ -5849,7 +5755,7 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
     const int fm = sp.bps > 16 ? 0 : decode_fork_mode();
     /* stereo frames above 16 bits: k_decode_sw first (serial above 16 bits), the other
      * instances then take only its hand-backs among them */
-    const bool sw = sp.bps > 16 && sp.bps <= 24 && fmt != BNF_OUT_FLACDECODER && !(ablate_flags() & BNF_ABLATE_NO_SW);
+    const bool sw = sp.bps > 16 && sp.bps <= 24 && fmt != BNF_OUT_FLACDECODER && !(bnf_ablate_flags() & BNF_ABLATE_NO_SW);
     std::unique_lock<std::mutex> lk(g_side_mu, std::defer_lock);
     SideQ *sq = nullptr;
     if (fm) {
@@ -5876,35 +5782,35 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
      * One launch after k_decode_st put both on the stream's critical path (C4 at 32 copies:
      * k_decode_st 11.7 ms, then k_decode<8> 6.3 ms, while the W16 / W32 grids ended at 10.9). */
     const bool w8split = sq && seg && cls && __atomic_load_n(&cls[3], __ATOMIC_RELAXED) != 0u &&
-                         !(ablate_flags() & BNF_ABLATE_NO_W8SPLIT);
+                         !(bnf_ablate_flags() & BNF_ABLATE_NO_W8SPLIT); /* open: the split stays on under BNF_ABLATE_NO_ST */
     const int nside = w8split ? 3 : 2;
     auto fork = [&]() -> hipError_t {
         hipError_t r = hipEventRecord(sq->fork, s);
         for (int i = 0; i < nside && r == hipSuccess; i++) r = hipStreamWaitEvent(sq->st[i], sq->fork, 0);
         if (r == hipSuccess)
-            r = bnf_launch_decode_tu2(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, sq->st[1]);
+            r = bnf_launch_decode_w32(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, sq->st[1]);
         if (r == hipSuccess)
-            r = bnf_launch_decode_tu5(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, sq->st[0]);
+            r = bnf_launch_decode_w16(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, sq->st[0]);
         if (r == hipSuccess && w8split)
-            r = bnf_launch_decode_tu1(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm,
+            r = bnf_launch_decode_w8(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm,
                                       mode | BNF_MODE_NOST, seg, sq->st[2]);
         for (int i = 0; i < nside && r == hipSuccess; i++) r = hipEventRecord(sq->join[i], sq->st[i]);
         return r;
     };
     if (sq && fm == 2 && e == hipSuccess) e = fork();
     if (sw) {
-        if (e == hipSuccess) e = bnf_launch_decode_sw_tu7(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, crcp, s);
+        if (e == hipSuccess) e = bnf_launch_decode_sw(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, crcp, s);
         mode |= BNF_MODE_SW;
     }
     if (e == hipSuccess)
         e = fmt == BNF_OUT_FLACDECODER
-                ? bnf_launch_decode_tu3(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, crcp, s)
-                : bnf_launch_decode_tu4(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, crcp, s);
+                ? bnf_launch_decode_st_fd(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, crcp, s)
+                : bnf_launch_decode_st_any(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, crcp, s);
     if (sq && fm == 1 && e == hipSuccess) e = fork();
     if (e == hipSuccess)
-        e = w8split ? bnf_launch_decode_tu1(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm,
+        e = w8split ? bnf_launch_decode_w8(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm,
                                             mode | BNF_MODE_STREDO, seg, s)
-                    : bnf_launch_decode_tu1(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, nullptr, s);
+                    : bnf_launch_decode_w8(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, nullptr, s);
     if (sq) {
         for (int i = 0; i < nside; i++) { /* joined even if a launch failed */
             const hipError_t ej = hipStreamWaitEvent(s, sq->join[i], 0);
@@ -5914,10 +5820,10 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
     } else if (seg_only) {
         g_seg_launches.fetch_add(1, std::memory_order_relaxed);
         if (e == hipSuccess)
-            e = bnf_launch_decode_seg_tu2(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
+            e = bnf_launch_decode_seg(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
     } else {
-        if (e == hipSuccess) e = bnf_launch_decode_tu5(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
-        if (e == hipSuccess) e = bnf_launch_decode_tu2(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
+        if (e == hipSuccess) e = bnf_launch_decode_w16(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
+        if (e == hipSuccess) e = bnf_launch_decode_w32(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
     }
     return e;
 }

@@ -1,0 +1,204 @@
+/*
+ * bnflac_launch.h -- everything the translation units of libbnflac.so say to each other,
+ * declared once: the kernels' `ablate` word, the per-TU table/stats entries, the decode
+ * launchers of the kernel TUs and the entry points of TU 0 that bnflac_runtime.cpp
+ * and bnflac_reader.cpp call.  Every file that defines or calls one of these includes this
+ * header, so the compiler checks each definition against its declaration (all of them are
+ * extern "C" and hidden: a drifted prototype would still link).
+ */
+#ifndef BNFLAC_LAUNCH_H
+#define BNFLAC_LAUNCH_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bnflac_device.h"
+
+/* ------------------------------------------------------------- the `ablate` word
+ * Every decode and parse kernel takes one uint32_t `ablate`.  It carries two disjoint fields:
+ *
+ *  - ablation bits (BNF_ABLATE_*), set by the user: bnflac_debug_set_ablate, or BNFLAC_ABLATE in
+ *    the environment (read once, at the first launch).  "exact" bits are A/B switches between
+ *    two implementations with identical PCM and records; "timing" bits skip work, and results
+ *    are wrong while one is set;
+ *  - mode bits (BNF_MODE_*), set by the launchers only: which of an instance's jobs a launch
+ *    does.  Never a user setting.
+ *
+ * A launcher passes (bnf_ablate_flags() & BNF_ABLATE_K_<family>) | (mode & BNF_MODE_K_<family>), so a user
+ * bit reaches only the kernels that define it and can never be read as a mode.  (Two of
+ * k_decode_sys's ablation bits have the numeric values of two of k_decode<W>'s mode bits; the
+ * family masks keep them apart.)
+ *
+ * This is the only list of the bits: include/bnflac.h, INTEGRATION.md and DESIGN.md point here. */
+
+/* timing: no frame CRC-16 (k_decode<W>, k_decode_st, k_decode_sw, k_decode_sys) */
+#define BNF_ABLATE_NO_CRC16 0x1u
+/* timing: no PCM stores (k_decode<W>, k_decode_st, k_decode_sw, k_decode_sys) */
+#define BNF_ABLATE_NO_STORE 0x2u
+/* timing: no restore (k_decode<W>, k_decode_sys: residuals stay in the rows; k_decode_st, k_decode_sw: every
+ * chunk through the generic steps) */
+#define BNF_ABLATE_NO_RESTORE 0x4u
+/* timing: no Rice decode (k_decode<W>, k_decode_st, k_decode_sw, k_decode_sys) */
+#define BNF_ABLATE_NO_RICE 0x8u
+/* timing: k_parse does not walk the subframes (and hands no CRC-16 prefix over) */
+#define BNF_ABLATE_NO_WALK 0x10u
+/* timing: k_parse's residual walk never refills its ring */
+#define BNF_ABLATE_NO_WALK_REFILL 0x20u
+/* exact: k_decode_st keeps no running CRC-16 of channel 1 in its chunk loop; the tail reads
+ * channel 1 again from k_parse's prefix on */
+#define BNF_ABLATE_NO_STFOLD 0x40u
+/* exact: the debug event counters and phase timers count (bnflac_debug_stats; k_decode<W>,
+ * k_decode_st, k_decode_sys) */
+#define BNF_ABLATE_STATS 0x100u
+/* exact: k_decode_st is not launched and k_decode<8> takes every stereo frame (the launcher
+ * of k_decode_st and k_decode<W> read it) */
+#define BNF_ABLATE_NO_ST 0x400u
+/* exact: every k_decode<W> chunk through the generic path, none through the fused one */
+#define BNF_ABLATE_NO_FUSED 0x800u
+/* exact: k_decode<W>'s 24-bit FLACFileReader wide flush (pack_wide24) off */
+#define BNF_ABLATE_NO_WIDE24 0x2000u
+/* exact, host only: k_decode_sw is not launched (bnf_launch_decode) */
+#define BNF_ABLATE_NO_SW 0x10000u
+/* exact: k_decode_sys restores every wave with the mixed-width variant (PM_MIXED) */
+#define BNF_ABLATE_SYS_MIXED 0x40000u
+/* timing: k_decode_sys's producer never refills ahead, it only lands */
+#define BNF_ABLATE_SYS_LAND_ONLY 0x80000u
+/* exact, host only: the W = 8 instance as one launch (bnf_launch_decode) */
+#define BNF_ABLATE_NO_W8SPLIT 0x100000u
+/* exact: k_decode_sys's producer takes no fast run, residual by residual */
+#define BNF_ABLATE_SYS_NO_RUN 0x200000u
+/* exact: k_decode_sys packs every chunk with the generic sys_pack */
+#define BNF_ABLATE_SYS_NO_PACK_FAST 0x400000u
+/* exact: k_parse's residual walk refills block by block (br_refill) on every refill */
+#define BNF_ABLATE_PARSE_BLKREFILL 0x800000u
+/* exact: k_decode_sys's producer refills every half chunk, 4 deep, instead of once per chunk */
+#define BNF_ABLATE_SYS_REFILL_HALF 0x1000000u
+/* timing: k_decode_st / k_decode_sw aim their PCM stores at a 513 KB window at the start of
+ * the output (an L2-resident footprint); ignored when out_bytes < 1 MiB */
+#define BNF_ABLATE_HOT_WINDOW 0x10000000u
+/* exact: k_decode_sw's FLACFileReader line flush off */
+#define BNF_ABLATE_SW_NO_LINE 0x20000000u
+
+/* Mode bit: the lane kernel decodes only the frames k_decode_sys handed back (BNF_FL_WAVE_REDO). */
+#define BNF_MODE_WREDO 0x4000u
+/* Mode bit: k_decode_sw ran before the other lane kernels (they take its SW frames only when
+ * it handed them back). */
+#define BNF_MODE_SW 0x8000u
+/* Mode bit: k_decode_list -- the frames of a device list (k_decode_sys's hand-backs), every
+ * class, decoded by this instance (no class split, stereo fast-path frames included). */
+#define BNF_MODE_LIST 0x20000u
+/* Mode bits of the W = 8 instance when its two jobs run as two launches (bnf_launch_decode):
+ * NOST -- the narrow non-stereo frames only (the decode order's class 1; beside k_decode_st,
+ * so it never reads a stereo frame's hand-back bit); STREDO -- only the stereo frames
+ * k_decode_st handed back (class 0; after it). */
+#define BNF_MODE_NOST 0x40000u
+#define BNF_MODE_STREDO 0x80000u
+/* Mode bit: k_decode_seg -- the W = 32 instance also takes the W16 class's blocks. */
+#define BNF_MODE_SEG 0x80000000u
+
+/* Per kernel family: the mode bits its launchers may set and the ablation bits it reads. */
+#define BNF_MODE_K_PARSE 0u
+#define BNF_ABLATE_K_PARSE (BNF_ABLATE_NO_WALK | BNF_ABLATE_NO_WALK_REFILL | BNF_ABLATE_PARSE_BLKREFILL)
+#define BNF_MODE_K_DECODE (BNF_MODE_WREDO | BNF_MODE_SW | BNF_MODE_LIST | BNF_MODE_NOST | BNF_MODE_STREDO | BNF_MODE_SEG)
+#define BNF_ABLATE_K_DECODE                                                                                      \
+    (BNF_ABLATE_NO_CRC16 | BNF_ABLATE_NO_STORE | BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE | BNF_ABLATE_STATS | \
+     BNF_ABLATE_NO_ST | BNF_ABLATE_NO_FUSED | BNF_ABLATE_NO_WIDE24)
+#define BNF_MODE_K_DECODE_ST (BNF_MODE_WREDO | BNF_MODE_SW)
+#define BNF_ABLATE_K_DECODE_ST                                                                                      \
+    (BNF_ABLATE_NO_CRC16 | BNF_ABLATE_NO_STORE | BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE | BNF_ABLATE_NO_STFOLD | \
+     BNF_ABLATE_STATS | BNF_ABLATE_NO_ST | BNF_ABLATE_HOT_WINDOW)
+#define BNF_MODE_K_DECODE_SW BNF_MODE_WREDO
+#define BNF_ABLATE_K_DECODE_SW                                                                                       \
+    (BNF_ABLATE_NO_CRC16 | BNF_ABLATE_NO_STORE | BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE | BNF_ABLATE_HOT_WINDOW | \
+     BNF_ABLATE_SW_NO_LINE)
+#define BNF_MODE_K_DECODE_SYS 0u
+#define BNF_ABLATE_K_DECODE_SYS                                                                                  \
+    (BNF_ABLATE_NO_CRC16 | BNF_ABLATE_NO_STORE | BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE | BNF_ABLATE_STATS | \
+     BNF_ABLATE_SYS_MIXED | BNF_ABLATE_SYS_LAND_ONLY | BNF_ABLATE_SYS_NO_RUN | BNF_ABLATE_SYS_NO_PACK_FAST |     \
+     BNF_ABLATE_SYS_REFILL_HALF)
+/* every launcher-owned bit */
+#define BNF_MODE_MASK (BNF_MODE_K_PARSE | BNF_MODE_K_DECODE | BNF_MODE_K_DECODE_ST | BNF_MODE_K_DECODE_SW | BNF_MODE_K_DECODE_SYS)
+
+static_assert(!(BNF_ABLATE_K_PARSE & BNF_MODE_K_PARSE), "k_parse: an ablation bit is a mode bit");
+static_assert(!(BNF_ABLATE_K_DECODE & BNF_MODE_K_DECODE), "k_decode<W>: an ablation bit is a mode bit");
+static_assert(!(BNF_ABLATE_K_DECODE_ST & BNF_MODE_K_DECODE_ST), "k_decode_st: an ablation bit is a mode bit");
+static_assert(!(BNF_ABLATE_K_DECODE_SW & BNF_MODE_K_DECODE_SW), "k_decode_sw: an ablation bit is a mode bit");
+static_assert(!(BNF_ABLATE_K_DECODE_SYS & BNF_MODE_K_DECODE_SYS), "k_decode_sys: an ablation bit is a mode bit");
+static_assert(!((BNF_ABLATE_NO_SW | BNF_ABLATE_NO_W8SPLIT) & BNF_MODE_MASK), "a host ablation bit is a mode bit");
+
+/* ------------------------------------------------------------- per-TU tables and counters
+ * Each kernel TU is its own code object with its own __constant__ CRC tables and g_stats
+ * (bnflac_kernels.hip defines the pair once; every TU instantiates it).  TU 0 keeps the table of
+ * these entries and loops over it in bnf_upload_tables and bnf_stats. */
+typedef struct {
+    hipError_t (*upload_tables)(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow);
+    hipError_t (*stats)(uint64_t *out16, int reset); /* adds the TU's g_stats to out16 */
+} bnf_tu_ops;
+/* (not const: hipcc would emit a const object with a constant initializer into the device code
+ * object as well, where the host functions it points to do not exist) */
+extern bnf_tu_ops bnf_ops_decode_w8, bnf_ops_decode_w16, bnf_ops_decode_w32, bnf_ops_decode_st_fd, bnf_ops_decode_st_any,
+    bnf_ops_decode_sw, bnf_ops_decode_sys;
+
+extern "C" {
+/* the user's ablation bits (the one g_ablate, in TU 0) */
+uint32_t bnf_ablate_flags(void);
+void bnf_set_ablate(uint32_t v);
+
+/* ------------------------------------------------------------- decode launchers (kernel TUs)
+ * perm: the decode order or nullptr; mode: BNF_MODE_* of the launch.
+ * seg: k_order's bucket ends (W = 16 / 32 only, with perm): blocks outside the class leave first */
+#define BNF_DECODE_ARGS                                                                                              \
+    const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp, uint32_t chn_lanes, int fmt,   \
+        uint8_t *out, uint64_t out_bytes, bnf_frame_info *info
+hipError_t bnf_launch_decode_w8(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *seg, hipStream_t s);
+hipError_t bnf_launch_decode_w16(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *seg, hipStream_t s);
+hipError_t bnf_launch_decode_w32(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *seg, hipStream_t s);
+/* k_decode_sys's hand-back list (W = 32: every order); nframes bounds the list */
+hipError_t bnf_launch_decode_list(BNF_DECODE_ARGS, const uint32_t *list, uint32_t mode, hipStream_t s);
+/* the W16 + W32 segment of the decode order (k_decode_seg; perm and seg required) */
+hipError_t bnf_launch_decode_seg(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *seg, hipStream_t s);
+/* stereo fast path (k_decode_st<FLACDECODER> / the other layouts); launched before k_decode<8>
+ * (it hands frames back to it).  crcp: k_parse's CRC-16 hand-off or nullptr */
+hipError_t bnf_launch_decode_st_fd(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *crcp, hipStream_t s);
+hipError_t bnf_launch_decode_st_any(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *crcp, hipStream_t s);
+/* stereo frames above 16 bits; launched before k_decode<8>/<16>/<32> (it hands frames back to k_decode<16>) */
+hipError_t bnf_launch_decode_sw(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t mode, const uint32_t *crcp, hipStream_t s);
+/* redo: [0] hand-back count (zeroed by the caller), [4..] the frames handed back */
+hipError_t bnf_launch_decode_sys(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t *redo, uint32_t mode, hipStream_t s);
+
+/* ------------------------------------------------------------- TU 0 (parse, index, dispatch): entry points */
+hipError_t bnf_upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow);
+hipError_t bnf_stats(uint64_t *out16, int reset);
+hipError_t bnf_launch_sync_scan(const uint8_t *d, uint64_t n, uint32_t *d_block_counts, uint32_t *d_total,
+                                uint64_t *d_out, uint32_t cap, hipStream_t s);
+uint32_t bnf_scan_blocks(uint64_t n);
+hipError_t bnf_launch_scan_u32(uint32_t *v, uint32_t n, uint32_t *total, hipStream_t s);
+int bnf_crc_mode(void);
+void bnf_set_crc_mode(int mode);    /* -1: env */
+void bnf_set_decode_sys(int mode);  /* -1: auto */
+void bnf_set_parse_wave(int mode);  /* -1: auto */
+uint64_t bnf_decode_seg_launches(void);
+hipError_t bnf_parse_wave_stats(uint64_t *out8, int reset);
+/* words: 16-byte aligned; the allocation must cover round_up(nbytes, 16) bytes.
+ * order: nullptr, or 256 + nframes words of device scratch for the frame order (k_order_*);
+ * crcp: nullptr, or k_parse's CRC-16 hand-off for these frames (8 words per frame) */
+hipError_t bnf_launch_parse(const uint32_t *words, uint64_t nbytes, const uint64_t *frame_offs, uint32_t nframes,
+                            bnf_stream_params sp, const uint64_t *out_sample_in, uint64_t base_sample,
+                            bnf_frame_info *info, uint32_t *order, uint32_t *crcp, bool *handed, hipStream_t s);
+hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
+                             uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
+                             uint32_t *order, const uint32_t *crcp, hipStream_t s);
+hipError_t bnf_launch_fill_bad(const bnf_frame_info *info, uint32_t nframes, bnf_stream_params sp, int fmt,
+                               uint8_t *out, uint64_t out_bytes, hipStream_t s);
+hipError_t bnf_launch_chain(const uint8_t *bytes, uint64_t nbytes, const uint64_t *cand, uint32_t ncand,
+                            const bnf_frame_info *info, uint64_t first_off, bnf_stream_params sp, uint32_t *gap_crc,
+                            int32_t *jump, uint32_t levels, uint32_t *mark, uint32_t *pos, uint64_t *bs, uint8_t *small,
+                            uint64_t *d_offs, uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *nframes,
+                            hipStream_t s);
+hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
+                                    bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
+                                    uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
+                                    uint32_t *d_status, hipStream_t s);
+} /* extern "C" */
+
+#endif

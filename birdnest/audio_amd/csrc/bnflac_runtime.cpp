@@ -25,6 +25,7 @@
 
 #include "../../../include/bnflac.h"
 #include "bnflac_device.h"
+#include "bnflac_launch.h"
 #include "bnflac_md5.h"
 
 static_assert(sizeof(bnflac_frame_info) == sizeof(bnf_frame_info), "frame info layout");
@@ -34,35 +35,6 @@ static_assert(offsetof(FLAC__FrameHeader, crc) == 32, "FrameHeader.Crc @32 (LibF
 static_assert(offsetof(FLAC__StreamMetadata, data) == 16, "StreamMetadata.data @16 (LibFLACSharp.cs:299)");
 static_assert(offsetof(FLAC__StreamMetadata, data.stream_info.sample_rate) == 32, "sample_rate @32");
 static_assert(offsetof(FLAC__StreamMetadata, data.stream_info.total_samples) == 48, "total_samples @48");
-
-extern "C" {
-hipError_t bnf_upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow);
-hipError_t bnf_launch_sync_scan(const uint8_t *d, uint64_t n, uint32_t *d_block_counts, uint32_t *d_total,
-                                uint64_t *d_out, uint32_t cap, hipStream_t s);
-uint32_t bnf_scan_blocks(uint64_t n);
-void bnf_set_ablate(uint32_t v);
-hipError_t bnf_stats(uint64_t *out16, int reset);
-hipError_t bnf_launch_parse(const uint32_t *words, uint64_t nbytes, const uint64_t *frame_offs,
-                            uint32_t nframes, bnf_stream_params sp, const uint64_t *out_sample_in,
-                            uint64_t base_sample, bnf_frame_info *info, uint32_t *order, uint32_t *crcp,
-                            bool *handed, hipStream_t s);
-/* order: nullptr, or 256 + nframes words of device scratch for the frame order (k_order_*);
- * crcp: nullptr, or k_parse's CRC-16 hand-off for these frames (8 words per frame) */
-hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nframes,
-                             bnf_stream_params sp, uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes,
-                             bnf_frame_info *info, uint32_t *order, const uint32_t *crcp, hipStream_t s);
-hipError_t bnf_launch_fill_bad(const bnf_frame_info *info, uint32_t nframes, bnf_stream_params sp, int fmt,
-                               uint8_t *out, uint64_t out_bytes, hipStream_t s);
-hipError_t bnf_launch_chain(const uint8_t *bytes, uint64_t nbytes, const uint64_t *cand, uint32_t ncand,
-                            const bnf_frame_info *info, uint64_t first_off, bnf_stream_params sp, uint32_t *gap_crc,
-                            int32_t *jump, uint32_t levels, uint32_t *mark, uint32_t *pos, uint64_t *bs, uint8_t *small,
-                            uint64_t *d_offs, uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *nframes,
-                            hipStream_t s);
-hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
-                                    bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
-                                    uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
-                                    uint32_t *d_status, hipStream_t s);
-}
 
 /* ------------------------------------------------------------------ errors */
 static thread_local std::string g_err;
@@ -136,10 +108,8 @@ static int ensure_device(int dev) {
     return 0;
 }
 
-/* Timing experiments only (bench.py --ablate): skip parts of the kernels.  Results are
- * wrong while non-zero.  bit0 CRC-16, bit1 PCM stores, bit2 restore, bit3 Rice decode,
- * bit4 k_parse subframe walk.  0x2000 is an exact A/B switch: the 24-bit FLACFileReader
- * wide flush (pack_wide24) off. */
+/* Timing experiments and exact A/B switches (bench.py --ablate); the bits are listed in
+ * bnflac_launch.h (BNF_ABLATE_*).  Results are wrong while a timing bit is set. */
 extern "C" BNFLAC_API void bnflac_debug_set_ablate(uint32_t flags) { bnf_set_ablate(flags); }
 /* 1 in a -DBNFLAC_CRC_FOLD_CHECK build (k_decode_st's tail computes the CRC-16 both ways and
  * counts the lanes that disagree, bnflac_debug_stats slot 7); 0 in the shipped library */
@@ -150,21 +120,15 @@ extern "C" BNFLAC_API int bnflac_debug_crc_fold_check(void) {
     return 0;
 #endif
 }
-extern "C" void bnf_set_parse_wave(int mode);
 /* parse kernel: -1 auto (k_parse_wave for small launches), 0 k_parse, 1 k_parse_wave (tests, A/B) */
 extern "C" BNFLAC_API void bnflac_debug_set_parse_wave(int mode) { bnf_set_parse_wave(mode); }
-extern "C" void bnf_set_decode_sys(int mode);
 /* k_decode_sys (systolic restore, every frame class): -1 auto (BNFLAC_DECODE_SYS), 0 the lane
  * kernels by class, 1 always (tests, A/B) */
 extern "C" BNFLAC_API void bnflac_debug_set_decode_sys(int mode) { bnf_set_decode_sys(mode); }
-extern "C" int bnf_crc_mode();
-extern "C" void bnf_set_crc_mode(int mode);
 /* the CRC-16 hand-off: -1 env BNFLAC_CRC_MODE (default 3), 0 none, 1 k_parse's prefix, 2 + its verdict,
  * 3 the prefix where it pays (bnf_launch_parse) */
 extern "C" BNFLAC_API void bnflac_debug_set_crc_mode(int mode) { bnf_set_crc_mode(mode); }
-extern "C" uint64_t bnf_decode_seg_launches();
 extern "C" BNFLAC_API uint64_t bnflac_debug_decode_seg_launches(void) { return bnf_decode_seg_launches(); }
-extern "C" hipError_t bnf_parse_wave_stats(uint64_t *out8, int reset);
 /* k_parse_wave's debug counters (collected when BNFLAC_PW_STATS is set): passes, splice rounds,
  * serial fallbacks, partitions, frames, wave-cycles in scans.  out8: 8 values. */
 extern "C" BNFLAC_API int bnflac_debug_parse_wave_stats(uint64_t *out8, int reset) {

@@ -560,7 +560,7 @@ DEV void sys_restore(SysShared &S, uint32_t w, uint32_t lane, uint32_t lg, uint3
     bool range_bad = false;
     SysPk pk;
     sys_pack_prep(pk, S, w, lane, lg, fmt, sp);
-    const bool tm = (ablate & 0x100u) != 0;
+    const bool tm = (ablate & BNF_ABLATE_STATS) != 0;
     uint64_t t_st = 0, t_pk = 0, t_bw = 0;
     sys_bar(); /* end of iteration 0: the producer's chunk 0 is in rows[0]; rows[1] may be overwritten */
     for (uint32_t k = 1; k <= nchunks; k++) {
@@ -570,7 +570,7 @@ DEV void sys_restore(SysShared &S, uint32_t w, uint32_t lane, uint32_t lg, uint3
         int32_t v[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) v[q] = row[(j + 4u * q) * SYS_RP + pl];
-        if (ablate & 4u) { /* timing ablation: no restore */
+        if (ablate & BNF_ABLATE_NO_RESTORE) { /* timing ablation: no restore */
         } else if (k == 1u) sys_steps<A, PM, true>(acc, rc, v, j, sh, wide, order);
         else sys_steps<A, PM, false>(acc, rc, v, j, sh, wide, order);
 #pragma unroll
@@ -583,8 +583,8 @@ DEV void sys_restore(SysShared &S, uint32_t w, uint32_t lane, uint32_t lg, uint3
         }
         lds_sync();
         const uint64_t t1 = sys_now(tm);
-        if (!(ablate & 2u)) {
-            if ((ablate & 0x400000u) || !sys_pack_fast(pk, row, n0, fmt, out)) sys_pack(S, row, w, lane, lg, n0, fmt, sp, out);
+        if (!(ablate & BNF_ABLATE_NO_STORE)) {
+            if ((ablate & BNF_ABLATE_SYS_NO_PACK_FAST) || !sys_pack_fast(pk, row, n0, fmt, out)) sys_pack(S, row, w, lane, lg, n0, fmt, sp, out);
         }
         const uint64_t t2 = sys_now(tm);
         sys_bar();
@@ -684,7 +684,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
         /* ---- subframe header: warm-ups into rows[0], coefficients into the table (rows[1]) */
         BR b;
         br_init(b, words, nbytes, (lds_u32 *)S.ring, lane, SYS_RD);
-        b.stats = (ablate & 0x100u) != 0; /* debug event counters (bench.py --stats) */
+        b.stats = (ablate & BNF_ABLATE_STATS) != 0; /* debug event counters (bench.py --stats) */
         STAT(b.stats, 5);
         RS rs;
         rs.verb = 0; rs.k = 0; rs.esc = 0; rs.left = 0; rs.pidx = 0; rs.nparts = 0; rs.psamples = 0;
@@ -767,7 +767,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
 #pragma unroll
         for (int i = 0; i <= SYS_RQMAX; i++) q.e[i] = b.iend;
         q.tw = q.dw = 0;
-        const bool rf_chunk = !(ablate & 0x1000000u); /* refill once per chunk, 2 deep (ablate: every half, 4 deep) */
+        const bool rf_chunk = !(ablate & BNF_ABLATE_SYS_REFILL_HALF); /* refill once per chunk, 2 deep (ablate: every half, 4 deep) */
         sys_bar(); /* B0: tables ready */
         /* ================================================= producer: chunks */
         const bool tm = b.stats;
@@ -785,7 +785,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
                     const uint32_t h0 = n0 + SYS_HALF * hh;
                     STAT(b.stats && active && h0 < bs, 4);
                     const uint64_t t0 = sys_now(tm);
-                    if (ablate & 0x80000u) { /* ablation: landings only */
+                    if (ablate & BNF_ABLATE_SYS_LAND_ONLY) { /* ablation: landings only */
                     } else if (rf_chunk) {
                         if (hh == 0) sys_refill<1>(b, active && h0 < bs, q, tm);
                     } else {
@@ -800,7 +800,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
                         if (run && rs.left == 0u && rs.pidx < rs.nparts) read_partition(b, rs);
                         kdirty = true;
                     }
-                    const bool fast = !(ablate & 0x200000u) && !any_lane(active && h0 < bs && !(run && !rs.esc && rs.left >= SYS_HALF));
+                    const bool fast = !(ablate & BNF_ABLATE_SYS_NO_RUN) && !any_lane(active && h0 < bs && !(run && !rs.esc && rs.left >= SYS_HALF));
                     if (fast && any_lane(run) && kdirty) {
                         kmax = active ? rs.k : 0u;
                         for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor(kmax, o));
@@ -825,7 +825,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
                     } else {
                         kdirty = true; /* rice_fused may read partition headers */
                         const uint32_t lo = max(h0, order), hi = active ? min(h0 + SYS_HALF, bs) : 0u;
-                        if (ablate & 8u) {
+                        if (ablate & BNF_ABLATE_NO_RICE) {
                             for (uint32_t n = lo; n < hi; n++) row[(n - n0) * SYS_RP] = 0;
                         } else {
                             for (uint32_t n = lo; n < hi; n++) row[(n - n0) * SYS_RP] = rice_fused(b, rs, limit, trunc, nullptr);
@@ -895,7 +895,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
         uint32_t ord = act ? S.p_order[pl] : 0u;
         for (int o = 32; o > 0; o >>= 1) ord = max(ord, (uint32_t)__shfl_xor(ord, o));
         const bool any_w = any_lane(act && (fl & SF_WIDE)), any_n = any_lane(act && !(fl & SF_WIDE));
-        const int pm = (ablate & 0x40000u) ? PM_MIXED : any_w ? (any_n ? PM_MIXED : PM_WIDE) : PM_NARROW;
+        const int pm = (ablate & BNF_ABLATE_SYS_MIXED) ? PM_MIXED : any_w ? (any_n ? PM_MIXED : PM_WIDE) : PM_NARROW;
         if (ord <= 4u) sys_restore_pm<1>(S, w, lane, lg, nchunks, fmt, sp, out, pm, ablate, words, nblk);
         else if (ord <= 8u) sys_restore_pm<2>(S, w, lane, lg, nchunks, fmt, sp, out, pm, ablate, words, nblk);
         else if (ord <= 16u) sys_restore_pm<4>(S, w, lane, lg, nchunks, fmt, sp, out, pm, ablate, words, nblk);
@@ -923,7 +923,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
         const uint64_t f_off = S.f_off[fl], end_byte = f_off + S.f_end[fl];
         const uint32_t crc_read = S.f_crc[fl];
         uint32_t acc = 0;
-        if (!(ablate & 1u)) {
+        if (!(ablate & BNF_ABLATE_NO_CRC16)) {
             if (!have_lanec) {
                 lanec = crc16_shift(1u, 16u * (63u - lane));
                 have_lanec = true;
@@ -959,40 +959,30 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
 }
 
 /* ------------------------------------------------------------------ host launcher */
-extern "C" {
-hipError_t bnf_upload_tables_tu8(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
-    return upload_tables(crc8, crc16x8, xpow);
-}
-void bnf_set_ablate_tu8(uint32_t v) { g_ablate.store(v, std::memory_order_relaxed); }
-hipError_t bnf_stats_tu8(uint64_t *out16, int reset) {
-    uint64_t v[16];
-    hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_stats), sizeof v);
-    if (e == hipSuccess) { /* slots 14, 15: refill wait cycles, DMA instructions waited past */
-        uint64_t d[4];
-        e = hipMemcpyFromSymbol(d, HIP_SYMBOL(g_sys_dbg), sizeof d);
-        v[14] += d[0];
-        v[15] += d[1];
-        if (e == hipSuccess && reset) {
-            static const uint64_t z4[4] = {0};
-            e = hipMemcpyToSymbol(HIP_SYMBOL(g_sys_dbg), z4, sizeof z4);
-        }
-    }
+/* g_stats as every TU, and on top slots 14, 15: refill wait cycles, DMA instructions waited past */
+static hipError_t sys_stats(uint64_t *out16, int reset) {
+    uint64_t d[4];
+    hipError_t e = hipMemcpyFromSymbol(d, HIP_SYMBOL(g_sys_dbg), sizeof d);
+    if (e == hipSuccess) e = tu_stats(out16, reset); /* nothing is touched when either read fails */
     if (e != hipSuccess) return e;
-    for (int i = 0; i < 16; i++) out16[i] += v[i];
+    out16[14] += d[0];
+    out16[15] += d[1];
     if (reset) {
-        static const uint64_t z[16] = {0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_stats), z, sizeof z);
+        static const uint64_t z4[4] = {0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_sys_dbg), z4, sizeof z4);
     }
     return e;
 }
+bnf_tu_ops bnf_ops_decode_sys = {tu_upload_tables, sys_stats};
+extern "C" {
 /* redo: [0] hand-back count (zeroed by the caller), [4..] the frames handed back */
-hipError_t bnf_launch_decode_sys_tu8(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
+hipError_t bnf_launch_decode_sys(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                      uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
                                      const uint32_t *perm, uint32_t *redo, uint32_t mode, hipStream_t s) {
     const uint32_t fpb = 64u / chn_lanes;
     const uint32_t nb = (nframes + fpb - 1u) / fpb;
     hipLaunchKernelGGL(k_decode_sys, dim3(nb), dim3(SYS_THREADS), 0, s, words, nbytes, nframes, sp, chn_lanes, fmt, out,
-                       out_bytes, info, perm, redo, ablate_flags() | mode);
+                       out_bytes, info, perm, redo, (bnf_ablate_flags() & BNF_ABLATE_K_DECODE_SYS) | (mode & BNF_MODE_K_DECODE_SYS));
     return hipGetLastError();
 }
 } /* extern "C" */

@@ -215,16 +215,14 @@ BNFLAC_API int bnflac_decode_parsed(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
                                     const bnflac_stream_params *sp, int out_format, uint8_t *d_out,
                                     uint64_t out_bytes, bnflac_frame_info *d_info, void *hip_stream);
 
-/* Timing experiments only: skip parts of the kernels (bit0 CRC-16, bit1 PCM stores,
- * bit2 restore, bit3 Rice decode, bit4 subframe walk).  Output is wrong while set.
- * Exception: bit 0x800 only routes every k_decode chunk through the generic path (exact).
- * Bit 0x10000000 aims k_decode_st's / k_decode_sw's PCM stores at a 513 KB window at the
- * start of d_out (an L2-resident footprint); it is ignored when out_bytes < 1 MiB.
- * Bit 0x40 is an exact A/B switch (identical PCM and records): k_decode_st keeps no running
- * CRC-16 of channel 1 in its chunk loop, and its tail reads channel 1 again from k_parse's
- * prefix on, as it did before the running remainder.
- * Bit 0x800000 is an exact A/B switch too: k_parse's residual walk refills its ring block by
- * block (all 8 slots tested on every refill, as before the 64-byte group form). */
+/* Development switch: the kernels' ablation bits.  "Timing" bits skip parts of the kernels
+ * (CRC-16, PCM stores, restore, Rice decode, the subframe walk): output is wrong while one is
+ * set.  "Exact" bits are A/B switches between two implementations with identical PCM and
+ * records (0x40 k_decode_st's running CRC-16 off, 0x800000 k_parse's block-by-block refill, ...).
+ * The one list of the bits, with what each does and which kernels read it, is
+ * birdnest/audio_amd/csrc/bnflac_launch.h (BNF_ABLATE_*).  Each kernel family receives only
+ * the bits it defines; the launchers' own mode bits cannot be set from here.  Also read once
+ * from BNFLAC_ABLATE in the environment. */
 BNFLAC_API void bnflac_debug_set_ablate(uint32_t flags);
 /* Debug: 1 when the library was built with -DBNFLAC_CRC_FOLD_CHECK (never the shipped one):
  * k_decode_st's tail then computes the frame's CRC-16 both from the running remainder and from

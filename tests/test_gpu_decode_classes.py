@@ -23,7 +23,7 @@ from tests.conftest import gpu_available
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FL_REDO = 16
+FL_REDO = 64  # BNF_FL_REDO (bnflac_device.h)
 
 
 @pytest.fixture(autouse=True)
@@ -67,16 +67,18 @@ def _mixed_batch(n_each, class1=False):
     return bytes(data), o, os_, np.concatenate(pcm), base
 
 
-def _decode(data, offs, osmp, total):
+def _decode(data, offs, osmp, total, sp=None):
+    """osmp None: frames positioned by their own sample numbers (a whole stream, sp its STREAMINFO)."""
     import torch
     from birdnest.audio_amd import libflac
     dev = torch.device("cuda:0")
-    sp = libflac.StreamParams(1, 4096, 4096, 44100, 2, 16, total)
+    if sp is None:
+        sp = libflac.StreamParams(1, 4096, 4096, 44100, 2, 16, total)
     n = len(data)
     d_bytes = torch.zeros((n + 3) // 4 * 4 + 16, dtype=torch.uint8, device=dev)
     d_bytes[:n] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
     d_offs = torch.from_numpy(offs).to(dev)
-    d_os = torch.from_numpy(osmp).to(dev)
+    d_os = torch.from_numpy(osmp).to(dev) if osmp is not None else None
     stride = libflac.out_stride(libflac.OUT_INTERLEAVED32, sp)
     d_out = torch.full((total * stride,), 0xAB, dtype=torch.uint8, device=dev)
     d_info = torch.zeros(len(offs) * libflac.FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
@@ -164,3 +166,48 @@ def test_w8_split_launches(n_each):
     finally:
         L.bnflac_debug_set_ablate(0)
     assert out1.tobytes() == out.tobytes() and info1.tobytes() == info.tobytes()
+
+
+FL_W32, FL_ST, FL_W16 = 16, 32, 128
+SYS_ONLY_BITS = 0x40000 | 0x80000  # bnflac_launch.h: BNF_ABLATE_SYS_MIXED | BNF_ABLATE_SYS_LAND_ONLY
+
+
+def _c4_64():
+    """BASELINE C4's shape at 64 frames: variable blocksize, every decode class."""
+    from birdnest.audio_amd import libflac, synth
+    from tests.test_gpu_parity import _stream_params
+    s = synth.encode(synth.config("C4", nframes=64, last_blocksize=0))
+    data = s.data.tobytes()
+    return data, s.frame_offsets.astype(np.int64), None, s.pcm, s.nsamples, _stream_params(libflac, data)
+
+
+@pytest.mark.skipif(not gpu_available(), reason="no GPU")
+@pytest.mark.parametrize("batch", ["c4_64", "mixed_class1"])
+def test_sys_ablate_bits_never_reach_lane_kernels(batch):
+    """k_decode_sys's ablation bits 0x40000 / 0x80000 have the numeric values of k_decode<8>'s
+    mode bits BNF_MODE_NOST / BNF_MODE_STREDO.  The launchers pass each kernel family only the
+    ablation bits it defines, so with the lane kernels forced a user who sets the two sys bits
+    gets the same records and PCM as with none (before the fields were separated, the W = 8
+    instance then took neither the class-1 frames nor k_decode_st's hand-backs).  The first
+    decode, with no bit set, also arms the W = 8 split for the second."""
+    from birdnest.audio_amd import libflac
+    L = libflac.load()
+    if batch == "c4_64":
+        data, offs, osmp, pcm, total, sp = _c4_64()
+    else:
+        data, offs, osmp, pcm, total = _mixed_batch(13, class1=True)
+        sp = None
+    L.bnflac_debug_set_ablate(0)
+    out, info = _decode(data, offs, osmp, total, sp)
+    fl = info["flags"]
+    assert (info["status"] == 0).all() and (info["crc_ok"] == 1).all()
+    assert (fl & FL_ST).any(), "the batch should hold stereo fast-path frames (BNF_FL_ST)"
+    assert ((fl & (FL_ST | FL_W16 | FL_W32)) == 0).any(), "the batch should hold class-1 frames"
+    assert np.array_equal(out.view("<i4").reshape(-1, 2), pcm)
+    L.bnflac_debug_set_ablate(SYS_ONLY_BITS)
+    try:
+        out1, info1 = _decode(data, offs, osmp, total, sp)
+    finally:
+        L.bnflac_debug_set_ablate(0)
+    assert info1.tobytes() == info.tobytes()
+    assert out1.tobytes() == out.tobytes()

@@ -1,6 +1,6 @@
 """Replay the MISMATCH lines of a tools/stress.py log on the GPU (debug tool, not a test):
 each stream is regenerated from its printed generator knobs, decoded through the batch API
-(interleaved32) with the fused k_decode path on and off (ablate 0x800), and compared with
+(interleaved32) with the fused k_decode path on and off (ablate bit BNF_ABLATE_NO_FUSED, csrc/bnflac_launch.h), and compared with
 the oracle frame by frame; the first differing frame/channel/sample is printed with the
 frame's record.  usage: python tools/dbg_kw.py gpurun_out/stress_x.log [more logs]
 BNFLAC_LIB_DIR=<dir> loads libbnflac.so from another build (A/B against an older commit)."""

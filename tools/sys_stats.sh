@@ -1,4 +1,4 @@
-# k_decode_sys phase timers and event counters (ablate 0x100) on C5 (8 files) and a 64-batch C2
+# k_decode_sys phase timers and event counters (ablate bit BNF_ABLATE_STATS, csrc/bnflac_launch.h) on C5 (8 files) and a 64-batch C2
 # step.  The timers need a variant build: BNFLAC_EXTRA_CFLAGS=-DBNFLAC_PHASE_TIMERS
 # BNFLAC_VARIANT_DIR=tools/_timers python -m birdnest.audio_amd.build; LIBS lists variant dirs.
 set -u
