@@ -31,6 +31,7 @@ HIP_TUS = [
     ("bnflac_kernels.hip", ["-DBNF_TU=5"], "bnflac_kernels_tu5"),  # k_decode<16>
     ("bnflac_kernels.hip", ["-DBNF_TU=7"], "bnflac_kernels_tu7"),  # k_decode_sw
     ("bnflac_sys.hip", [], "bnflac_sys"),  # k_decode_sys (TU 8; includes bnflac_kernels.hip)
+    ("bnflac_md5.hip", [], "bnflac_md5"),  # k_md5_streams (no CRC tables, no g_stats)
     ("bnflac_runtime.cpp", [], "bnflac_runtime"),
     ("bnflac_reader.cpp", [], "bnflac_reader"),
 ]

@@ -199,6 +199,14 @@ hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const
                                     bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
                                     uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
                                     uint32_t *d_status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_md5.hip (no tables, no g_stats, no ablate word)
+ * k_md5_streams: stream s is the sample frames [bounds[s], bounds[s + 1]) of pcm, `unit` bytes
+ * each.  src 0: those bytes are the MD5 message; src 1..4: they are int32 samples and the message
+ * is the low src bytes of each.  Zeroes status (4 words) on s, then launches. */
+hipError_t bnf_launch_md5_streams(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t unit, uint32_t src,
+                                  const uint64_t *bounds, uint32_t nstreams, const uint8_t *expected, uint8_t *md5,
+                                  uint32_t *verdict, uint32_t *status, hipStream_t s);
 } /* extern "C" */
 
 #endif

@@ -242,6 +242,35 @@ extern "C" BNFLAC_API int bnflac_md5_interleaved32(const int32_t *pcm, uint64_t 
     return 0;
 }
 
+extern "C" BNFLAC_API uint32_t bnflac_md5_layout(int fmt, const bnflac_stream_params *sp) {
+    if (!sp || sp->channels < 1 || sp->channels > FLAC__MAX_CHANNELS || sp->bps < 4 || sp->bps > 32) return 0;
+    const uint32_t B = (sp->bps + 7) / 8;
+    switch (fmt) {
+    case BNFLAC_OUT_INTERLEAVED32: return B;
+    case BNFLAC_OUT_FLACDECODER: return sp->bps == 16 && sp->channels <= 2 ? B : 0; /* 16-bit samples, 1-2 channels */
+    case BNFLAC_OUT_FILEREADER: return sp->bps == 16 || sp->bps == 24 ? B : 0;      /* bps / 8 bytes, every channel */
+    default: return 0; /* PLANAR32 is channel-major per frame: it needs the frame table */
+    }
+}
+
+extern "C" BNFLAC_API int bnflac_md5_streams(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
+                                             const bnflac_stream_params *sp, const uint64_t *d_stream_samples,
+                                             uint32_t nstreams, const uint8_t *d_expected, uint8_t *d_md5,
+                                             uint32_t *d_verdict, uint32_t *d_status, void *hs) {
+    if (!ctx || !sp) return fail("bnflac_md5_streams: null argument");
+    DevGuard dg(ctx->device); /* the launch on the context's device */
+    if (!d_status || (nstreams && (!d_stream_samples || !d_md5))) return fail("bnflac_md5_streams: null output");
+    if (pcm_bytes && !d_pcm) return fail("bnflac_md5_streams: null d_pcm");
+    if (((uintptr_t)d_pcm) & 15u) return fail("bnflac_md5_streams: d_pcm must be 16-byte aligned");
+    if (nstreams >= (1u << 30)) return fail("bnflac_md5_streams: too many streams");
+    const uint32_t B = bnflac_md5_layout(fmt, sp);
+    if (!B) return fail("bnflac_md5_streams: layout does not carry the MD5 bytes");
+    const bool int32_src = fmt == BNFLAC_OUT_INTERLEAVED32;
+    hipError_t e = bnf_launch_md5_streams(d_pcm, pcm_bytes, bnflac_out_stride(fmt, sp), int32_src ? B : 0, d_stream_samples,
+                                          nstreams, d_expected, d_md5, d_verdict, d_status, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_md5_streams: ") + hipGetErrorString(e));
+}
+
 extern "C" BNFLAC_API int bnflac_index_frames(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
                                               uint64_t *d_offsets, uint32_t cap, uint32_t *d_count, void *hs) {
     if (!ctx) return fail("bnflac_index_frames: null ctx");

@@ -126,7 +126,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_index_frames", "bnflac_decode_frames", "bnflac_parse_frames", "bnflac_decode_parsed",
                  "bnflac_out_stride", "bnflac_debug_set_ablate", "bnflac_debug_stats", "bnflac_debug_set_parse_wave", "bnflac_debug_parse_wave_stats",
                  "bnflac_debug_set_decode_sys", "bnflac_debug_decode_seg_launches", "bnflac_md5_interleaved32", "bnflac_index_stream",
-                 "bnflac_index_streams",
+                 "bnflac_index_streams", "bnflac_md5_layout", "bnflac_md5_streams",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -212,6 +212,9 @@ def load() -> ctypes.CDLL:
     L.bnflac_reader_last_error.restype = ctypes.c_char_p
     L.bnflac_md5_interleaved32.restype = i
     L.bnflac_md5_interleaved32.argtypes = [p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, p]
+    L.bnflac_md5_layout.restype, L.bnflac_md5_layout.argtypes = ctypes.c_uint32, [i, p]
+    L.bnflac_md5_streams.restype = i
+    L.bnflac_md5_streams.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, p, p, p, p, p]
     _LIB = L
     return L
 
@@ -367,6 +370,19 @@ def md5_interleaved32(pcm: np.ndarray, channels: int, bps: int) -> bytes:
     return bytes(out)
 
 
+def md5_layout(fmt: int, sp: StreamParams) -> int:
+    """Bytes per sample of the MD5 message when md5_streams can hash fmt's bytes for sp, else 0."""
+    return int(load().bnflac_md5_layout(fmt, ctypes.byref(sp)))
+
+
+def streaminfo_md5(data) -> bytes:
+    """The md5sum field of a stream that starts with fLaC and its STREAMINFO block (bytes 26..42)."""
+    data = bytes(data[:42])
+    if len(data) < 42 or data[:4] != b"fLaC" or data[4] & 0x7F != 0:
+        raise ValueError("not a FLAC stream that starts with a STREAMINFO block")
+    return data[26:42]
+
+
 class BatchDecoder:
     """Device-pointer batch decode (bnflac_decode_frames) over torch CUDA tensors."""
 
@@ -481,6 +497,35 @@ class BatchDecoder:
                                          self._stream(stream))
         if rc != 0:
             raise RuntimeError(self.L.bnflac_last_error().decode())
+
+    def md5_streams(self, d_pcm, fmt: int, sp: StreamParams, d_stream_samples, nstreams: int, d_expected=None,
+                    stream=None, pcm_bytes=None):
+        """STREAMINFO md5sum of every stream of a decoded batch, on the device (bnflac_md5_streams).
+        d_stream_samples: int64[nstreams + 1] sample-frame bounds (index_streams' d_stream_samples);
+        d_expected: uint8[nstreams * 16] or None; pcm_bytes: the decoded size (default: all of d_pcm).
+        -> (d_md5 uint8[n, 16], d_verdict int32[n], d_status int32[4]), all on the device and not
+        synchronised, like index_streams."""
+        import torch
+        dev = d_pcm.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        nbytes = d_pcm.numel() * d_pcm.element_size()
+        if d_stream_samples.numel() < nstreams + 1 or d_stream_samples.element_size() != 8:
+            raise ValueError("d_stream_samples must hold nstreams + 1 64-bit bounds")
+        if d_expected is not None and d_expected.numel() * d_expected.element_size() < 16 * nstreams:
+            raise ValueError("d_expected must hold 16 bytes per stream")
+        with torch.cuda.stream(s):
+            d_md5 = torch.zeros((nstreams, 16), dtype=torch.uint8, device=dev)
+            d_verdict = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        rc = self.L.bnflac_md5_streams(self.ctx, ctypes.c_void_p(d_pcm.data_ptr()),
+                                       nbytes if pcm_bytes is None else min(pcm_bytes, nbytes), fmt, ctypes.byref(sp),
+                                       ctypes.c_void_p(d_stream_samples.data_ptr()), nstreams,
+                                       ctypes.c_void_p(d_expected.data_ptr()) if d_expected is not None else None,
+                                       ctypes.c_void_p(d_md5.data_ptr()), ctypes.c_void_p(d_verdict.data_ptr()),
+                                       ctypes.c_void_p(d_status.data_ptr()), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_md5, d_verdict, d_status
 
     def crc_handoff(self, nframes: int) -> np.ndarray:
         """Debug: the CRC-16 hand-off of the last parse_frames call, [nframes, 8] uint32."""

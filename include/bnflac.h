@@ -269,6 +269,27 @@ BNFLAC_API uint32_t bnflac_out_stride(int out_format, const bnflac_stream_params
 BNFLAC_API int bnflac_md5_interleaved32(const int32_t *pcm, uint64_t nsamples, uint32_t channels, uint32_t bps,
                                         uint8_t out_md5[16]);
 
+/* Bytes per sample of the STREAMINFO MD5 message when out_format's bytes can be hashed by
+ * bnflac_md5_streams for sp, else 0 (PLANAR32; FLACDECODER unless 16-bit with 1-2 channels;
+ * FILEREADER unless 16- or 24-bit; bps outside 4..32).  Host only, no GPU needed. */
+BNFLAC_API uint32_t bnflac_md5_layout(int out_format, const bnflac_stream_params *sp);
+
+/* STREAMINFO md5sum of every stream of a decoded batch, on the device.  Stream s is the sample
+ * frames [d_stream_samples[s], d_stream_samples[s + 1]) of d_pcm in out_format (nstreams + 1
+ * entries: what bnflac_index_streams writes; for one stream, {0, total}).  d_pcm 16-byte aligned,
+ * its allocation at least round_up(pcm_bytes, 4) bytes.
+ * d_md5: 16 bytes per stream.  d_expected (may be NULL): 16 bytes per stream, STREAMINFO's sums.
+ * d_verdict (may be NULL), one word per stream: 0 equal, 1 differs, 2 not checked (d_expected NULL
+ * or all zero: libFLAC's "not computed"), 3 range descending or past pcm_bytes (sum written as
+ * zeros).  d_status, 4 words: [0] bit 0 = some stream had verdict 3, [1] streams equal,
+ * [2] streams differing, [3] streams not checked.  Hashes whatever the decode left in the range
+ * (a CRC-failed frame's zeros, as libFLAC does).  nstreams == 0 writes a zero status.
+ * Asynchronous on hip_stream, no host synchronisation. */
+BNFLAC_API int bnflac_md5_streams(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int out_format,
+                                  const bnflac_stream_params *sp, const uint64_t *d_stream_samples,
+                                  uint32_t nstreams, const uint8_t *d_expected, uint8_t *d_md5,
+                                  uint32_t *d_verdict, uint32_t *d_status, void *hip_stream);
+
 /* ======================== Part 3: streaming reader ======================= */
 
 /* The fast path under FLACDecoder.Read (FLACDecoder.cs:124-205) and OpenAL's buffer fill
