@@ -19,18 +19,19 @@ LIB = os.path.join(PKG, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
 # The translation units of libbnflac.so: (source under csrc/, extra -D flags, object name).
-# bnflac_kernels.hip is built once per BNF_TU.  This is the only description of the build: the
+# bnflac_kernels.hip is built once per instance, and the define names what the object holds;
+# bnflac_sys.hip includes the headers it uses.  This is the only description of the build: the
 # compile jobs, the staleness check and source_hash() all derive from it and from the listing
-# of csrc/ below.
+# of csrc/ below.  (The rows keep the link order the library has always had.)
 HIP_TUS = [
-    ("bnflac_kernels.hip", ["-DBNF_TU=0"], "bnflac_kernels_tu0"),  # sync scan, parse, both indexers, frame orders, the dispatcher
-    ("bnflac_kernels.hip", ["-DBNF_TU=1"], "bnflac_kernels_tu1"),  # k_decode<8>
-    ("bnflac_kernels.hip", ["-DBNF_TU=2"], "bnflac_kernels_tu2"),  # k_decode<32>, k_decode_list, k_decode_seg
-    ("bnflac_kernels.hip", ["-DBNF_TU=3"], "bnflac_kernels_tu3"),  # k_decode_st<FLACDECODER>
-    ("bnflac_kernels.hip", ["-DBNF_TU=4"], "bnflac_kernels_tu4"),  # k_decode_st<other layouts>
-    ("bnflac_kernels.hip", ["-DBNF_TU=5"], "bnflac_kernels_tu5"),  # k_decode<16>
-    ("bnflac_kernels.hip", ["-DBNF_TU=7"], "bnflac_kernels_tu7"),  # k_decode_sw
-    ("bnflac_sys.hip", [], "bnflac_sys"),  # k_decode_sys (TU 8; includes bnflac_kernels.hip)
+    ("bnflac_kernels.hip", ["-DBNF_K_PARSE"], "bnflac_parse"),  # sync scan, parse, both indexers, frame orders, the dispatcher
+    ("bnflac_kernels.hip", ["-DBNF_DEC_W=8"], "bnflac_decode_w8"),  # k_decode<8>
+    ("bnflac_kernels.hip", ["-DBNF_DEC_W=32"], "bnflac_decode_w32"),  # k_decode<32>, k_decode_list, k_decode_seg
+    ("bnflac_kernels.hip", ["-DBNF_ST_FD=1"], "bnflac_decode_st_fd"),  # k_decode_st<FLACDECODER>
+    ("bnflac_kernels.hip", ["-DBNF_ST_FD=0"], "bnflac_decode_st_any"),  # k_decode_st<other layouts>
+    ("bnflac_kernels.hip", ["-DBNF_DEC_W=16"], "bnflac_decode_w16"),  # k_decode<16>
+    ("bnflac_kernels.hip", ["-DBNF_K_SW"], "bnflac_decode_sw"),  # k_decode_sw
+    ("bnflac_sys.hip", [], "bnflac_sys"),  # k_decode_sys
     ("bnflac_md5.hip", [], "bnflac_md5"),  # k_md5_streams (no CRC tables, no g_stats)
     ("bnflac_runtime.cpp", [], "bnflac_runtime"),
     ("bnflac_reader.cpp", [], "bnflac_reader"),
@@ -102,7 +103,7 @@ def build_hip(force=False, verbose=False):
         if vdir:
             base += os.environ.get("BNFLAC_EXTRA_CFLAGS", "").split()
         jobs, objs = [], []
-        # development shortcut: BNFLAC_DEV_TUS="bnflac_kernels_tu1,bnflac_sys" recompiles only
+        # development shortcut: BNFLAC_DEV_TUS="bnflac_decode_w8,bnflac_sys" recompiles only
         # those kernel objects (and the host .cpp files) and reuses the others as they are
         # (never set for a real build)
         dev = os.environ.get("BNFLAC_DEV_TUS")

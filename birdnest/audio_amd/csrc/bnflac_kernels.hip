@@ -19,390 +19,20 @@
  *                   W = 8 serves frames whose LPC orders are all <= 8 (register ring
  *                   of 8, low VGPR count); W = 32 the rest.
  *
- * Bit reader.  Every lane owns an 8-slot ring of 16-byte blocks of its own bitstream in
- * LDS, filled by exec-masked LDS-DMA (global_load_lds_dwordx4) once per 32-sample
- * chunk; a chunk decodes from blocks that landed during the previous chunk, so HBM
- * latency is hidden behind a whole chunk of work and the per-codeword cursor advance
- * is branch-free (one ds_read_b32).  Words outside the landed range are read from
- * global memory directly (rare: jumps, very high bit rates).
+ * The lane bit reader (BR, the LDS-DMA ring) is bnf_bitreader.h.
  *
  * Integer-only, HBM/issue bound; no MFMA.  Bit-exactness is defined
  * by oracle/flac_oracle.c, which restates the same DLL behaviour on the CPU.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
-#include <type_traits>
 
-#include "bnflac_device.h"
-#include "bnflac_launch.h" /* the `ablate` word (BNF_ABLATE_*, BNF_MODE_*) and every cross-TU declaration */
-
-#define DEV __device__ __forceinline__
-
-/* ------------------------------------------- CRC tables (CRC-8; slice-by-8 CRC-16 for k_decode<W>, k_decode_sys) */
-/* Tables are filled by the host at module load (bnflac_runtime.cpp) into these: */
-__constant__ uint8_t g_crc8_tab[256];
-__constant__ uint16_t g_crc16_tab[8][256]; /* slice-by-8 */
-__constant__ uint16_t g_crc16_xpow[40];    /* x^(8*2^j) mod P for j < 40 */
-/* Debug event counters (wave-level events, enabled by ablate bit 0x100; timing runs
- * leave them off).  0 fused chunks, 1 generic chunks, 2 DMA landing waits, 3 slow Rice
- * codewords, 4 refills, 5 waves, 6 k_decode_st tails that continued the running CRC-16 (lanes),
- * 7 of those, the ones whose remainder differs from the re-read's (-DBNFLAC_CRC_FOLD_CHECK
- * builds only, with or without 0x100). */
-__device__ unsigned long long g_stats[16]; /* 8.. : s_memtime cycles per phase, summed over waves */
-/* Phase timers (s_memtime) for the debug counters; compiled in only with
- * -DBNFLAC_PHASE_TIMERS, because a scalar-memory op anywhere in the loop makes hipcc's
- * LDS waits conservative (lgkmcnt(0)). */
-DEV uint64_t tnow(bool on) { /* call at wave-uniform points only */
-#ifndef BNFLAC_PHASE_TIMERS
-    (void)on;
-    return 0ull;
-#endif
-    if (!on) return 0ull;
-    const uint64_t t = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return t;
-}
-#define STAT(on, i) do { if (on) { if (__builtin_amdgcn_read_exec() && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) atomicAdd(&g_stats[i], 1ull); } } while (0)
-
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-/* LDS accesses to buffers that are never LDS-DMA targets, as inline asm: hipcc cannot tell
- * them from the DMA'd ring and would drain every vector-memory op (vmcnt(0)) first.
- * Completion is waited for explicitly (lds_sync / lgkmcnt). */
-DEV void lds_st128(const void *a, u32x4 v) {
-    asm volatile("ds_write_b128 %0, %1" ::"v"((uint32_t)(uintptr_t)a), "v"(v) : "memory");
-}
-DEV u32x4 lds_ld128(const void *a) { /* result valid after s_waitcnt lgkmcnt(0) */
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)a) : "memory");
-    return v;
-}
-DEV void lds_st128(const lds_u32x4 *a, u32x4 v) {
-    asm volatile("ds_write_b128 %0, %1" ::"v"((uint32_t)(uintptr_t)a), "v"(v) : "memory");
-}
-DEV u32x4 lds_ld128(const lds_u32x4 *a) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)a) : "memory");
-    return v;
-}
-DEV void lds_st64(const void *a, uint64_t v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"((uint32_t)(uintptr_t)a), "v"(v) : "memory");
-}
-DEV uint64_t lds_ld64(const void *a) {
-    uint64_t v;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)a) : "memory");
-    return v;
-}
-typedef __attribute__((address_space(1))) const void gvoid;
-/* 16-byte global store through an integer address: the address-space cast keeps it a
- * global_store (a generic pointer would make it a flat store, which also counts in
- * lgkmcnt -- every later LDS wait would then wait for the HBM write) */
-DEV void gst128(uint64_t addr, u32x4 v) { *(__attribute__((address_space(1))) u32x4 *)addr = v; }
-
-
-/* ----------------------------------------------------------------- bit reader */
-#define RING_MAX 16       /* 16-byte slots per lane (k_parse and k_decode_st use 8) */
-#define RING_LANE_DW 256  /* dwords per slot row (64 lanes x 4) */
-
-/* MSB-first bit stream.  Window hi:lo (big-endian words); the cursor is 32-s bits into
- * hi (s in [0,31]; s == 0 means the cursor sits at the start of lo), so the next 32 bits
- * are alignbit(hi, lo, s) for every cursor position.  nx = raw (little-endian) word wi,
- * the next to enter the window; it is re-read from the ring on every advance. */
-struct BR {
-    const uint32_t *__restrict__ w; /* stream words (16-byte aligned base) */
-    uint32_t nw;                    /* words readable (allocation covers nblk*4) */
-    uint32_t nblk;                  /* 16-byte blocks readable */
-    lds_u32 *ring;                  /* slot 0 of lane 0 (wave-uniform) */
-    lds_u32 *lring;                 /* this lane's word-0 entry */
-    uint32_t rdepth, wmask;         /* ring slots (power of 2 <= RING_MAX); ring word mask */
-    uint32_t wi, s, hi, lo, nx;
-    uint32_t vendw, iend;           /* words < vendw landed in the ring; blocks < iend issued */
-    uint32_t iend_old;              /* k_decode's 2-deep DMA pipeline: issued two refills ago */
-    uint32_t ra, vlim;              /* k_decode_st: ring byte address of word wi (with the lane's bits), vendw - 1 */
-    bool stats;
-};
-
-DEV void br_init(BR &b, const uint32_t *words, uint64_t nbytes, lds_u32 *ring, uint32_t lane, uint32_t rdepth) {
-    b.rdepth = rdepth;
-    b.wmask = 4u * rdepth - 1u;
-    b.w = words;
-    b.nblk = (uint32_t)((nbytes + 15u) >> 4);
-    b.nw = b.nblk * 4u;
-    b.ring = ring;
-    b.lring = ring + lane * 4u;
-    b.wi = 2;
-    b.s = b.hi = b.lo = b.nx = 0;
-    b.vendw = b.iend = 0;
-    b.iend_old = 0;
-    b.stats = false;
-}
-
-DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-/* vmcnt retires in issue order (loads, stores and LDS-DMA together): waiting until at most
- * N are outstanding completes everything older than the youngest N */
-template <int N> DEV void wait_vm_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-/* the same with a wave-uniform run-time count (vmcnt is an immediate: jump table) */
-DEV void wait_vm_n(uint32_t n) {
-    switch (__builtin_amdgcn_readfirstlane(min(n, 63u))) {
-#define WVN(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-#define WVN8(k) WVN(k) WVN(k + 1) WVN(k + 2) WVN(k + 3) WVN(k + 4) WVN(k + 5) WVN(k + 6) WVN(k + 7)
-        WVN8(0) WVN8(8) WVN8(16) WVN8(24) WVN8(32) WVN8(40) WVN8(48) WVN8(56)
-#undef WVN8
-#undef WVN
-    default: break;
-    }
-}
-/* single-wave workgroups: LDS exchange between lanes needs only the LDS queue drained
- * (and the compiler kept from reordering); no s_barrier, no vmcnt drain of stores/DMA */
-DEV void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-DEV uint32_t gword(const BR &b, uint32_t w) { return (w < b.nw) ? b.w[w] : 0u; }
-/* ring layout [slot][lane][4 words] (16 bytes per lane per slot, the LDS-DMA dwordx4
- * image); block j lives in slot j % rdepth */
-DEV uint32_t ring_off(const BR &b, uint32_t w) { /* dword offset of word w from lring */
-    return ((w & (b.wmask & ~3u)) << 6) + (w & 3u);
-}
-DEV uint32_t ring_word(const BR &b, uint32_t w) { return b.lring[ring_off(b, w)]; }
-/* LDS-DMA destination invariant.  A global_load_lds_dwordx4 writes lane l's 16 bytes at
- * (destination base + 16 l); round 2 found that a base that is not 1 KiB aligned writes the
- * wrong LDS bytes with no fault (wrong PCM).  Every ring slot row is one
- * whole 1 KiB image, so the invariant is: ring bases 1 KiB aligned (LDS_DMA_ALIGN on every
- * __shared__ ring) and slot offsets multiples of 1 KiB (the static_asserts below).  Debug
- * builds (-DBNFLAC_DEBUG_ASSERTS) also check every base at run time. */
-#define LDS_DMA_ALIGN __attribute__((aligned(1024)))
-static_assert(RING_LANE_DW * 4 == 1024, "a ring slot row must be exactly one 1 KiB LDS-DMA image");
-DEV void dma_check_base(const lds_u32 *base) {
-#ifdef BNFLAC_DEBUG_ASSERTS
-    if (((uint32_t)(uintptr_t)base & 1023u) != 0u) __builtin_trap();
-#else
-    (void)base;
-#endif
-}
-/* One LDS-DMA: 16 bytes per lane to dst + 16 lane.  (Issued as inline asm instead, hidden from
- * the waitcnt pass, it measured 1-2% slower on k_decode_st in round 4.) */
-DEV void lds_dma16(const void *g, lds_u32 *dst) {
-    dma_check_base(dst);
-    __builtin_amdgcn_global_load_lds((gvoid *)g, (lds_void *)dst, 16, 0, 0);
-}
-DEV void dma_block(const BR &b, uint32_t j, uint32_t slot) { /* one 16-byte block per lane */
-    lds_dma16(b.w + (uint64_t)min(j, b.nblk - 1u) * 4u, b.ring + slot * RING_LANE_DW);
-}
-/* The same with the instruction's immediate offset (one address for consecutive blocks).  The
- * offset moves the LDS destination as well as the global address (measured on gfx950,
- * tools/dbg_glds_off.hip), so the LDS base passed is the slot row minus the offset: the
- * row still receives lane l's 16 bytes at +16 l. */
-template <int OFF>
-DEV void lds_dma16_off(const void *g, lds_u32 *row) {
-    dma_check_base(row); /* the row the data lands in (the base passed is row - OFF / 4) */
-    __builtin_amdgcn_global_load_lds((gvoid *)g, (lds_void *)(row - OFF / 4), 16, OFF, 0);
-}
-
-/* Issue the blocks this lane will need next (exec-masked LDS-DMA per ring slot).  Blocks
- * issued earlier have landed once the wait returns.  The block of word wi is kept: br_adv
- * re-reads it. */
-template <int KEEP = 0> /* KEEP: younger vector-memory ops (PCM stores) that may stay in flight */
-DEV void br_refill(BR &b) {
-    wait_vm_but<KEEP>();
-    b.vendw = b.iend * 4u;
-    /* whole 64-byte lines: [iend, first line of the cursor + rdepth); a 4-slot ring (one
-     * line) refills from the cursor's block instead */
-    const uint32_t need = b.rdepth >= 8u ? ((b.wi >> 2) & ~3u) : (b.wi >> 2);
-    const uint32_t lo = max(b.iend, need), hi = need + b.rdepth;
-#pragma unroll 1 /* rare path (seeks, landings), inlined at every cursor advance: keep it small */
-    for (int s = 0; s < RING_MAX; s++) {
-        if ((uint32_t)s >= b.rdepth) break; /* wave-uniform */
-        const uint32_t j = lo + (((uint32_t)s - lo) & (b.rdepth - 1u));
-        if (j < hi) dma_block(b, j, (uint32_t)s);
-    }
-    b.iend = max(b.iend, hi);
-}
-
-/* Rare path: word wi is not in the landed part of the ring (a jump, or a lane that
- * consumed more than the ring held): wait for what is in flight, refill if still short. */
-DEV void br_drained(BR &b) { /* every vector-memory op of this wave has completed (per lane) */
-    b.vendw = b.iend * 4u;
-    b.iend_old = b.iend;
-}
-DEV void br_land(BR &b, uint32_t margin = 0) { /* afterwards words wi .. wi + margin have landed */
-    STAT(b.stats, 2);
-    wait_vm();
-    br_drained(b);
-    if (b.wi + margin >= b.vendw) {
-        br_refill(b);
-        wait_vm();
-        br_drained(b);
-    }
-}
-
-/* Blocking seek (subframe starts, skips). */
-DEV void br_seek(BR &b, uint64_t bit) {
-    b.s = (uint32_t)(0u - bit) & 31u;
-    const uint32_t hw = (uint32_t)((bit + b.s) >> 5) - 1u; /* word holding the cursor (-1 at bit 0) */
-    b.hi = __builtin_bswap32(gword(b, hw));
-    b.lo = __builtin_bswap32(gword(b, hw + 1u));
-    b.wi = hw + 2u;
-    b.iend = (b.wi >> 2) & ~3u;
-    br_refill(b);
-    wait_vm();
-    br_drained(b);
-    b.nx = ring_word(b, b.wi);
-}
-
-/* k_decode's refill: a 2-deep pipeline.  Waits only for the DMAs issued two refills ago
- * (vmcnt counts loads, stores and LDS-DMA together and retires them in issue order, so
- * letting the younger q.s_last + q.d_last + q.s_prev ops stay outstanding is exact), marks
- * those blocks landed, and issues the next blocks.  Blocks issued now become readable two
- * chunks later; the ring keeps ~6 blocks ahead of the cursor.  Called by the whole wave
- * (the counts must be wave-uniform); `want` masks the lanes that refill.  A full drain in
- * between (br_land, seek) only completes more, so the counts stay safe without reset. */
-struct VmQ {
-    uint32_t d_last, s_last, s_prev; /* DMAs of the last refill; stores since it; before it */
-};
-DEV void br_refill2(BR &b, bool want, VmQ &q, bool nowait = false) {
-    if (!nowait) wait_vm_n(q.s_last + q.d_last + q.s_prev); /* nowait: timing ablation 0x200 only */
-    if (want) b.vendw = b.iend_old * 4u;
-    /* the ring holds rdepth/4 whole lines; a lane whose cursor (word wi) is in the newest
-     * line fetches the next line into the oldest line's slots: 4 x 16-byte DMAs hitting
-     * one cache line */
-    const uint32_t curl = (b.wi >> 2) & ~3u;
-    const bool go = want && b.iend <= curl + 4u;
-    const uint32_t slot0 = b.iend & (b.rdepth - 1u); /* multiple of 4 */
-    uint32_t d = 0;
-#pragma unroll
-    for (int h = 0; h < RING_MAX / 4; h++) {
-        if ((uint32_t)(h * 4) >= b.rdepth) break; /* wave-uniform */
-        const bool gh = go && slot0 == (uint32_t)(h * 4);
-        if (__any(gh)) { /* wave-uniform: the 4 DMAs below are issued exactly when this holds */
-            d += 4;
-            if (gh) {
-#pragma unroll
-                for (int k = 0; k < 4; k++) dma_block(b, b.iend + k, (uint32_t)(h * 4 + k));
-            }
-        }
-    }
-    if (want) {
-        b.iend_old = b.iend;
-        if (go) b.iend += 4u;
-    }
-    q.s_prev = q.s_last;
-    q.s_last = 0;
-    q.d_last = d;
-}
-
-/* k_decode's refill (1-deep): br_issue, after a chunk's entropy phase, fetches the 16-byte
- * blocks up to rdepth past the block of the cursor word (never that block's slot, which
- * br_adv re-reads), so at least (rdepth - 1) * 16 bytes lie ahead of the cursor; br_wait1,
- * before the next entropy phase, waits for them -- only the PCM stores packed since (at
- * least q.s_last of them, all younger) may stay in flight -- and marks them landed.  The
- * restore and the pack run in between.  A lane that needs more within one chunk lands
- * (br_land). */
-DEV void br_wait1(BR &b, VmQ &q) {
-    wait_vm_n(q.s_last);
-    b.vendw = b.iend * 4u;
-    q.s_last = 0;
-}
-DEV void br_issue(BR &b, bool want) {
-    const uint32_t cb = b.wi >> 2;
-    const uint32_t lo = max(b.iend, cb), hi = cb + b.rdepth;
-#pragma unroll
-    for (int k = 0; k < RING_MAX; k++) {
-        if ((uint32_t)k >= b.rdepth) break; /* wave-uniform */
-        const uint32_t j = lo + (((uint32_t)k - lo) & (b.rdepth - 1u)); /* the block for slot k */
-        const bool go = want && j < hi;
-        if (__any(go)) {
-            if (go) dma_block(b, j, (uint32_t)k);
-        }
-    }
-    if (want) b.iend = max(b.iend, hi);
-}
-
-DEV uint64_t br_pos(const BR &b) { return ((uint64_t)(b.wi - 1u) << 5) - b.s; }
-DEV uint32_t br_peek(const BR &b) { return __builtin_amdgcn_alignbit(b.hi, b.lo, b.s); }
-/* Pending LDS store carried into the next cursor advance (fused decode): issuing it after
- * the window update and before the next ring read keeps every LDS op covered by the next
- * lgkmcnt wait a whole codeword old. */
-struct PendW {
-    int32_t *at;
-    int32_t v;
-    bool on;
-};
-DEV bool any_lane(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; } /* wave-uniform */
-/* leading zeros, ~0u for 0 (v_ffbh_u32; asm so the compiler assumes no range).  An asm
- * statement makes hipcc's waitcnt pass wait lgkmcnt(0) before it; the builtin form
- * (x ? clz(x) : ~0u, also one v_ffbh_u32) keeps counted waits but measured 1-2% slower on
- * k_decode_st (round 4) and no different on k_decode_sys. */
-DEV uint32_t ffbh(uint32_t x) {
-    uint32_t r;
-    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
-
-template <bool CHECK = true>
-DEV void br_adv(BR &b, uint32_t n, PendW *pw = nullptr) { /* n <= 32; branch-free except the rare landing check */
-    const int32_t t = (int32_t)b.s - (int32_t)n;
-    const bool c = t < 0;
-    b.s = (uint32_t)t & 31u;
-    b.hi = c ? b.lo : b.hi;
-    b.lo = c ? __builtin_bswap32(b.nx) : b.lo;
-    b.wi += c ? 1u : 0u;
-    if (CHECK && __builtin_expect(any_lane(b.wi >= b.vendw), 0)) br_land(b);
-    if (pw && pw->on) *pw->at = pw->v;
-    /* issue the ring read after the window update (an artificial data dependency of the
-     * address on the new lo), so the wait for the previous word (one codeword old) is not
-     * merged with a wait for this one; other instructions stay free to move */
-    uint32_t off = ring_off(b, b.wi);
-    asm volatile("" : "+v"(off) : "v"(b.lo));
-    b.nx = b.lring[off];
-}
-template <bool CHECK = true>
-DEV uint32_t br_read(BR &b, uint32_t n) { /* 0..32 bits */
-    uint32_t v = n ? (br_peek(b) >> ((32u - n) & 31u)) : 0u;
-    br_adv<CHECK>(b, n);
-    return v;
-}
-template <bool CHECK = true>
-DEV int32_t br_read_s(BR &b, uint32_t n) {
-    uint32_t v = br_read<CHECK>(b, n);
-    uint32_t s = (32u - n) & 31u;
-    return (int32_t)(v << s) >> s;
-}
-DEV void br_skip(BR &b, uint64_t n) {
-    if (n <= 32) br_adv(b, (uint32_t)n);
-    else br_seek(b, br_pos(b) + n);
-}
-/* count zeros up to and including the terminating 1 (read_unary_unsigned @0x10001960) */
-DEV bool br_unary(BR &b, uint32_t &q, uint64_t limit) {
-    uint32_t acc = 0;
-    for (;;) {
-        uint32_t p = br_peek(b);
-        if (p) {
-            uint32_t z = (uint32_t)__builtin_clz(p);
-            acc += z;
-            br_adv(b, z + 1u);
-            q = acc;
-            return true;
-        }
-        acc += 32u;
-        br_adv(b, 32u);
-        if (br_pos(b) > limit) {
-            q = acc;
-            return false;
-        }
-    }
-}
-
-DEV uint8_t crc8_bytes(const uint8_t *p, uint32_t n) {
-    uint8_t c = 0;
-    for (uint32_t i = 0; i < n; i++) c = g_crc8_tab[c ^ p[i]];
-    return c;
-}
+#include "bnf_bitreader.h" /* and bnf_common.h: the tables, g_stats, the LDS helpers; the lane bit reader BR */
+#include "bnf_crc16.h"
+#include "bnf_crc16_tab.h"
+#include "bnf_frame.h"
+#include "bnf_residual.h"
 
 /* ------------------------------------------------------ wave-uniform bit reader */
 /* The reader of the wave-per-frame kernels (k_parse_wave): one cursor for the whole wave
@@ -508,484 +138,6 @@ DEV bool br_unary(WR &r, uint32_t &q, uint64_t limit) { /* read_unary_unsigned @
     }
 }
 
-/* ------------------------------------------------------------ frame header */
-enum { E_LOST_SYNC = 0, E_BAD_HEADER = 1, E_CRC = 2, E_UNPARSEABLE = 3 };
-
-/* read_frame_header_ @0x10011d70: fills fi; returns BNF_ST_* (OK also when the header
- * is flagged unparseable -- the caller reports that after the number conversion). */
-template <class R> /* R: BR (lane cursor) or WR (wave-uniform cursor) */
-DEV uint32_t parse_header(R &b, uint64_t fbit, uint64_t limit, const bnf_stream_params &sp,
-                          bnf_frame_info &fi) {
-    /* the header's CRC-8 is folded in as each byte is read (no byte buffer: a per-lane array
-     * indexed at run time would live in scratch memory) */
-    uint32_t crc = 0, last = 0, b2 = 0, b3 = 0;
-    auto take = [&](uint32_t v) { crc = g_crc8_tab[crc ^ v]; last = v; };
-    uint32_t unparseable = 0, bs_hint = 0, sr_hint = 0, x;
-    br_seek(b, fbit);
-    take(br_read(b, 8));
-    const uint32_t b1 = br_read(b, 8);
-    take(b1);
-    fi.cached = -1;
-    if (b1 & 0x02) unparseable = 1;
-    for (int i = 0; i < 2; i++) {
-        x = br_read(b, 8);
-        if (x == 0xff) {
-            fi.cached = 0xff;
-            fi.err = E_BAD_HEADER;
-            fi.resume_bit = br_pos(b);
-            return BNF_ST_ERROR;
-        }
-        take(x);
-        if (i == 0) b2 = x;
-        else b3 = x;
-    }
-    x = b2 >> 4;
-    if (x == 0) unparseable = 1;
-    else if (x == 1) fi.blocksize = 192;
-    else if (x <= 5) fi.blocksize = 576u << (x - 2);
-    else if (x <= 7) bs_hint = x;
-    else fi.blocksize = 256u << (x - 8);
-    x = b2 & 0x0f;
-    switch (x) {
-    case 0:
-        if (sp.has_stream_info) fi.sample_rate = sp.sample_rate;
-        else unparseable = 1;
-        break;
-    case 1: fi.sample_rate = 88200; break;
-    case 2: fi.sample_rate = 176400; break;
-    case 3: fi.sample_rate = 192000; break;
-    case 4: fi.sample_rate = 8000; break;
-    case 5: fi.sample_rate = 16000; break;
-    case 6: fi.sample_rate = 22050; break;
-    case 7: fi.sample_rate = 24000; break;
-    case 8: fi.sample_rate = 32000; break;
-    case 9: fi.sample_rate = 44100; break;
-    case 10: fi.sample_rate = 48000; break;
-    case 11: fi.sample_rate = 96000; break;
-    case 15:
-        fi.err = E_BAD_HEADER;
-        fi.resume_bit = br_pos(b);
-        return BNF_ST_ERROR;
-    default: sr_hint = x; break;
-    }
-    x = b3 >> 4;
-    if (x & 8) {
-        fi.channels = 2;
-        if ((x & 7) <= 2) fi.assignment = (x & 7) + 1;
-        else unparseable = 1;
-    } else {
-        fi.channels = x + 1;
-        fi.assignment = 0;
-    }
-    x = (b3 & 0x0e) >> 1;
-    switch (x) {
-    case 0:
-        if (sp.has_stream_info) fi.bps = sp.bps;
-        else unparseable = 1;
-        break;
-    case 1: fi.bps = 8; break;
-    case 2: fi.bps = 12; break;
-    case 4: fi.bps = 16; break;
-    case 5: fi.bps = 20; break;
-    case 6: fi.bps = 24; break;
-    default: unparseable = 1; break;
-    }
-    if (b3 & 0x01) unparseable = 1;
-    /* UTF-8 frame/sample number (@0x10001e20 / @0x10001f60), with libFLAC's truthiness tests */
-    const bool is64 = (b1 & 0x01) || (sp.has_stream_info && sp.min_blocksize != sp.max_blocksize);
-    {
-        uint64_t v = 0;
-        uint32_t n;
-        bool bad = false;
-        x = br_read(b, 8);
-        take(x);
-        if (!(x & 0x80)) { v = x; n = 0; }
-        else if ((x & 0xC0) && !(x & 0x20)) { v = x & 0x1F; n = 1; }
-        else if ((x & 0xE0) && !(x & 0x10)) { v = x & 0x0F; n = 2; }
-        else if ((x & 0xF0) && !(x & 0x08)) { v = x & 0x07; n = 3; }
-        else if ((x & 0xF8) && !(x & 0x04)) { v = x & 0x03; n = 4; }
-        else if ((x & 0xFC) && !(x & 0x02)) { v = x & 0x01; n = 5; }
-        else if (is64 && (x & 0xFE) && !(x & 0x01)) { v = 0; n = 6; }
-        else { bad = true; n = 0; }
-        for (; !bad && n; n--) {
-            x = br_read(b, 8);
-            take(x);
-            if (!(x & 0x80) || (x & 0x40)) bad = true;
-            else v = (v << 6) | (x & 0x3F);
-        }
-        if (!is64 && !bad) v &= 0xffffffffull; /* 32-bit accumulation (6 bytes max => 31 bits) */
-        if (bad) {
-            fi.cached = (int32_t)last;
-            fi.err = E_BAD_HEADER;
-            fi.resume_bit = br_pos(b);
-            return BNF_ST_ERROR;
-        }
-        fi.number_type = is64 ? 1u : 0u;
-        fi.number = v;
-    }
-    if (bs_hint) {
-        x = br_read(b, 8);
-        take(x);
-        if (bs_hint == 7) {
-            uint32_t y = br_read(b, 8);
-            take(y);
-            x = (x << 8) | y;
-        }
-        fi.blocksize = x + 1;
-    }
-    if (sr_hint) {
-        x = br_read(b, 8);
-        take(x);
-        if (sr_hint != 12) {
-            uint32_t y = br_read(b, 8);
-            take(y);
-            x = (x << 8) | y;
-        }
-        fi.sample_rate = (sr_hint == 12) ? x * 1000u : (sr_hint == 13 ? x : x * 10u);
-    }
-    x = br_read(b, 8);
-    fi.crc8 = x;
-    if (br_pos(b) > limit) return BNF_ST_TRUNC;
-    if (crc != (x & 0xffu)) {
-        fi.err = E_BAD_HEADER;
-        fi.resume_bit = br_pos(b);
-        return BNF_ST_ERROR;
-    }
-    /* the frame->sample number conversion can also flag UNPARSEABLE (@0x10012372):
-     * fixed-number header, no fixed block size yet, STREAMINFO min != max.  That
-     * combination is impossible (min != max forces 64-bit numbers), so only the
-     * header-field flag remains; the host replays the conversion itself. */
-    fi.unparseable = unparseable;
-    if (unparseable) {
-        fi.err = E_UNPARSEABLE;
-        fi.resume_bit = br_pos(b);
-        return BNF_ST_ERROR;
-    }
-    return BNF_ST_OK;
-}
-
-DEV uint32_t sub_bps(const bnf_frame_info &fi, uint32_t ch) {
-    uint32_t bps = fi.bps;
-    if ((fi.assignment == 1 && ch == 1) || (fi.assignment == 2 && ch == 0) || (fi.assignment == 3 && ch == 1)) bps++;
-    return bps;
-}
-
-/* ------------------------------------------------------------ subframe parse */
-enum { T_CONST = 0, T_VERB = 1, T_FIXED = 2, T_LPC = 3 };
-enum { P_MMX16 = 0, P_IA32 = 1, P_WIDE = 2 };
-
-struct SubHdr {
-    uint32_t type, order, wasted, bps; /* bps after removing wasted bits */
-    uint32_t prec;
-    int32_t shift;
-    uint32_t porder, rice2;
-    int32_t cval;
-    uint32_t path;
-};
-
-/* read_subframe_ @0x10012480 up to (and including) the residual coding header.
- * STORE: warm-ups go to warm[u * WS] and coefficients to coef[u] for u < NW, in loops
- * unrolled to NW (compile-time indices: register arrays stay in registers).  Returns
- * BNF_ST_*; on ERROR sets err and the reader position is where libFLAC stops. */
-template <bool STORE, int NW = 32, int WS = 1, class R = BR>
-DEV uint32_t parse_subframe_head(R &b, uint32_t bps, uint32_t bs, uint64_t limit, SubHdr &h,
-                                 int32_t *warm, int32_t *coef, int32_t &err) {
-    uint32_t x = br_read(b, 8);
-    uint32_t wflag = x & 1u;
-    x &= 0xFEu;
-    h.wasted = 0;
-    if (wflag) {
-        uint32_t u;
-        if (!br_unary(b, u, limit)) return BNF_ST_TRUNC;
-        h.wasted = u + 1u;
-        if (h.wasted > bps) { err = E_UNPARSEABLE; return BNF_ST_ERROR; }
-        bps -= h.wasted;
-    }
-    if (x & 0x80) { err = E_LOST_SYNC; return BNF_ST_ERROR; }
-    if (bps > 32) { err = E_UNPARSEABLE; return BNF_ST_ERROR; }
-    h.bps = bps;
-    h.order = 0;
-    h.porder = 0;
-    h.rice2 = 0;
-    h.path = P_IA32;
-    if (x == 0) {
-        h.type = T_CONST;
-        h.cval = br_read_s(b, bps);
-        return BNF_ST_OK;
-    }
-    if (x == 2) { h.type = T_VERB; return BNF_ST_OK; }
-    if (x < 16) { err = E_UNPARSEABLE; return BNF_ST_ERROR; }
-    if (x <= 24) {
-        h.type = T_FIXED;
-        h.order = (x >> 1) & 7u;
-    } else if (x < 64) {
-        err = E_UNPARSEABLE;
-        return BNF_ST_ERROR;
-    } else {
-        h.type = T_LPC;
-        h.order = ((x >> 1) & 31u) + 1u;
-    }
-    if (STORE) {
-#pragma unroll
-        for (int u = 0; u < NW; u++)
-            if ((uint32_t)u < h.order) warm[u * WS] = br_read_s(b, bps);
-        for (uint32_t u = NW; u < h.order; u++) br_read_s(b, bps);
-    } else {
-        for (uint32_t u = 0; u < h.order; u++) br_read_s(b, bps);
-    }
-    if (h.type == T_LPC) {
-        uint32_t p = br_read(b, 4);
-        if (p == 15) { err = E_LOST_SYNC; return BNF_ST_ERROR; }
-        h.prec = p + 1;
-        h.shift = br_read_s(b, 5);
-        if (STORE) {
-#pragma unroll
-            for (int u = 0; u < NW; u++)
-                if ((uint32_t)u < h.order) coef[u] = br_read_s(b, h.prec);
-            for (uint32_t u = NW; u < h.order; u++) br_read_s(b, h.prec);
-        } else {
-            for (uint32_t u = 0; u < h.order; u++) br_read_s(b, h.prec);
-        }
-        uint32_t ilog = 31u - (uint32_t)__builtin_clz(h.order);
-        if (bps + h.prec + ilog <= 32) h.path = (bps <= 16 && h.prec <= 16 && h.order >= 4) ? P_MMX16 : P_IA32;
-        else h.path = P_WIDE;
-    }
-    uint32_t m = br_read(b, 2);
-    if (m > 1) { err = E_UNPARSEABLE; return BNF_ST_ERROR; }
-    h.rice2 = m;
-    h.porder = br_read(b, 4);
-    /* read_residual_partitioned_rice_ sanity checks (@0x10012e1e, @0x10012e41) */
-    if (h.porder == 0) {
-        if (bs < h.order) { err = E_LOST_SYNC; return BNF_ST_ERROR; }
-    } else {
-        if ((bs >> h.porder) < h.order) { err = E_LOST_SYNC; return BNF_ST_ERROR; }
-        if (bs & ((1u << h.porder) - 1u)) { err = E_UNPARSEABLE; return BNF_ST_ERROR; } /* see oracle */
-    }
-    return br_pos(b) > limit ? BNF_ST_TRUNC : BNF_ST_OK;
-}
-
-DEV uint32_t st_hmask(uint32_t h, uint32_t o) { /* little-endian dword at line offset o: bytes below h cleared */
-    return h <= o ? ~0u : (h >= o + 4u ? 0u : (~0u << (8u * (h - o))));
-}
-/* ------------------------------------------------- CRC-16 remainder arithmetic
- * (the table-free zero test, st_crc16_ok below, and k_parse's prefix of it) */
-struct CrcZ {
-    uint32_t r0, r1, px; /* remainder mod T^4; XOR of every word (parity) */
-};
-DEV void crcz_w(CrcZ &c, uint32_t le) { /* one little-endian stream word */
-    const uint32_t W = __builtin_bswap32(le);
-    const uint32_t H = __builtin_amdgcn_alignbit(c.r1, c.r0, 28);
-    const uint32_t n0 = W ^ H ^ (H << 4);
-    c.r1 = c.r0 ^ (H >> 28);
-    c.r0 = n0;
-}
-DEV void crcz_blk(CrcZ &c, uint4 v) {
-    c.px ^= v.x ^ v.y ^ v.z ^ v.w;
-    crcz_w(c, v.x);
-    crcz_w(c, v.y);
-    crcz_w(c, v.z);
-    crcz_w(c, v.w);
-}
-/* k_parse's part of a 2-channel frame's CRC-16 (round 6).  The decode kernels' tail re-reads
- * the whole frame for the CRC-16, and every wave of a CU reaches its tail together, so those
- * bytes go at the HBM rate with nothing beside them.  k_parse walks subframe 0 anyway: its ring
- * holds those bytes, so it folds every whole 64-byte line before subframe 1's line into the
- * same T^4 remainder (from the ring while the line is one of its two, else one reload, L2-warm),
- * one 16-byte block at a time (three live state words: k_parse's occupancy is LDS-bound at 5
- * waves per SIMD, ~100 VGPRs), and the decode tail continues from there, re-reading only the
- * rest of the frame. */
-/* The prefix state: the remainder mod Q(y) = y^15 + y + 1, y = x^32, in 15 words.  Q(y) =
- * T(x^32) = T(x)^32 is a multiple of T, so it keeps M mod T; with whole words as the
- * coefficients a 64-byte line is 18 word XORs at once (S y^16 + sum W[i] y^(15-i): y^15 = y + 1,
- * y^16 = y^2 + y; checked against bit-serial division mod T in Python while writing this)
- * against 96 VALU through the T^4 form, and the words are taken as loaded (little-endian): a
- * byte swap permutes the bits of every word alike, so it is applied to the 15 state words
- * once, at the hand-off (crcp_z).  k_parse<1> 128 VGPRs, 4 waves per SIMD: C2 k_parse 2.52 ->
- * 2.16 ms against the T^4 form (1.95 without a prefix), C3 the same as with it (10.43 vs
- * 10.47 ms per step; a build at 146 VGPRs, 3 waves, had cost C3's plain walk 0.5 ms). */
-struct CrcP {
-    uint32_t s[15]; /* s[k]: the coefficient of y^k (little-endian words) */
-    uint32_t px;    /* XOR of every word (parity) */
-    uint32_t wc;    /* next line to fold (absolute 64-byte line index); ~0: no prefix for this frame */
-};
-DEV void crcp_init(CrcP &c) {
-#pragma unroll
-    for (int k = 0; k < 15; k++) c.s[k] = 0u;
-    c.px = 0u;
-    c.wc = ~0u;
-}
-DEV void crcp_fold(CrcP &c, const u32x4 (&v)[4]) {
-    const uint32_t W[16] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w,
-                            v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w};
-    c.px ^= W[0] ^ W[1] ^ W[2] ^ W[3] ^ W[4] ^ W[5] ^ W[6] ^ W[7] ^ W[8] ^ W[9] ^ W[10] ^ W[11] ^ W[12] ^ W[13] ^
-            W[14] ^ W[15];
-    const uint32_t r0 = c.s[13] ^ c.s[14] ^ W[15] ^ W[0], r1 = c.s[0] ^ c.s[13] ^ W[14] ^ W[0],
-                   r2 = c.s[0] ^ c.s[1] ^ c.s[14] ^ W[13];
-#pragma unroll
-    for (int d = 14; d >= 3; d--) c.s[d] = c.s[d - 2] ^ c.s[d - 1] ^ W[15 - d]; /* descending: old s[d-2], s[d-1] */
-    c.s[2] = r2;
-    c.s[1] = r1;
-    c.s[0] = r0;
-    c.wc++;
-}
-/* the remainder in the decode tails' T^4 form (st_crc16_ok continues it) */
-DEV CrcZ crcp_z(const CrcP &c) {
-    CrcZ z{0u, 0u, 0u};
-#pragma unroll
-    for (int k = 14; k >= 0; k--) crcz_w(z, c.s[k]);
-    z.px = c.px;
-    return z;
-}
-/* fold the lines before line cl (whole wave).  The ring holds the two lines [iend / 4 - 2,
- * iend / 4), and the refill keeps the line of word wi (the reader's next word) and the one
- * after it: so before a refill, cl = wi / 16 -- every line the reader has loaded, which the
- * refill may overwrite -- folds from the ring (a line behind a landing refill reads again
- * from global memory, L2-warm; bounding by the cursor's bit position instead left 22% of C2's
- * lines to that path: the word lookahead crosses a line first).  The frame's first line is
- * folded before the walk (parse_frame), so these are whole lines. */
-template <bool ALL = false, class C> /* ALL: every line before cl (the walk's end); else at most one (a refill point) */
-DEV void crcp_hook(C &c, const BR &b, uint32_t lane, uint32_t cl) {
-    for (uint32_t it = 0; any_lane(c.wc < cl) && (ALL || it == 0u); it++) {
-        if (c.wc < cl) {
-            const uint32_t L = c.wc;
-            u32x4 v[4];
-            if (L + 2u >= (b.iend >> 2)) {
-#pragma unroll
-                for (uint32_t i = 0; i < 4; i++)
-                    v[i] = lds_ld128((const lds_u32x4 *)(b.ring + (((L & 1u) * 4u + i) * RING_LANE_DW) + lane * 4u));
-                lds_sync();
-                crcp_fold(c, v);
-            } else { /* overwritten by a refill: read it again (each path folds: no merge of v) */
-                const u32x4 *g = (const u32x4 *)((const uint8_t *)b.w + (uint64_t)L * 64u);
-#pragma unroll
-                for (uint32_t i = 0; i < 4; i++) v[i] = g[i];
-                crcp_fold(c, v);
-            }
-        }
-    }
-}
-
-#define CRC_LINES 4 /* 64-byte lines in flight per lane: each lane walks its own frame */
-
-/* Zero test of the CRC-16 remainder of [b0, b1), the frame with its footer (read_frame_'s
- * check @0x10011a01: the footer equals the CRC of the frame bytes iff the CRC of frame + footer
- * is zero), by arithmetic, with no tables (round 6).  P = x^16 + x^15 + x^2 + 1 = (x + 1) T with
- * T = x^15 + x + 1, so M = 0 mod P iff M has even parity and M = 0 mod T.  The remainder mod
- * T^4 = x^60 + x^4 + 1 (a multiple of T) costs five VALU per 32-bit word: with the state
- * r = r1:r0 (60 bits; r1's top four bits are stale copies of bits alignbit already took),
- * r x^32 + W = (r0 mod x^28) x^32 + W + H (x^4 + 1), H = r >> 28.  Leading zero bytes leave M
- * unchanged and trailing ones multiply it by a power of x (invertible mod T), so whole 16-byte
- * blocks with the bytes outside [b0, b1) cleared give the same verdict.  The 11-bit LDS tables
- * this replaces cost 0.75 bank-conflicted lookups per byte on the CU's one LDS pipe. */
-DEV uint32_t byte_keep(int32_t lo, int32_t hi, int32_t w) { /* bytes 4w..4w+3 kept iff in [lo, hi) */
-    const int32_t a = min(max(lo - 4 * w, 0), 4), b = min(max(hi - 4 * w, 0), 4);
-    const uint32_t mlo = a >= 4 ? 0u : (0xFFFFFFFFu << (8 * a));
-    const uint32_t mhi = b >= 4 ? 0xFFFFFFFFu : ((1u << (8 * b)) - 1u);
-    return mlo & mhi;
-}
-DEV bool crcz_zero(const CrcZ &c) {
-    if (__builtin_popcount(c.px) & 1) return false;
-    uint64_t v = ((uint64_t)(c.r1 & 0x0FFFFFFFu) << 32) | c.r0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { /* x^15 = x + 1: degree 59 -> 45 -> 31 -> 17 -> 14 */
-        const uint64_t h = v >> 15;
-        v = (v & 0x7FFFu) ^ h ^ (h << 1);
-    }
-    return v == 0;
-}
-/* the 64-byte line at q into the remainder, its bytes below h cleared (h = 0: whole line) */
-DEV void crcz_line(CrcZ &c, uint4 (&v)[4], uint32_t h) {
-    if (h) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            v[u].x &= st_hmask(h, 16u * u);
-            v[u].y &= st_hmask(h, 16u * u + 4u);
-            v[u].z &= st_hmask(h, 16u * u + 8u);
-            v[u].w &= st_hmask(h, 16u * u + 12u);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) crcz_blk(c, v[u]);
-}
-/* CRC-16 verdict of [b0, b1) with NL 64-byte lines in flight per lane, continuing c, which
- * already holds the lines [b0 & ~63, from) (from: a line boundary) */
-template <int NL = CRC_LINES>
-DEV bool st_crc16_ok(const uint8_t *__restrict__ bytes, uint64_t b0, uint64_t b1, CrcZ c = CrcZ{0u, 0u, 0u},
-                     uint64_t from = 0, CrcZ *fin = nullptr) { /* fin: the final remainder (check builds) */
-    const uint64_t p0 = max(b0 & ~(uint64_t)63u, from);
-    const uint32_t h = p0 < b0 ? (uint32_t)(b0 & 63u) : 0u;
-    const uint32_t nl = b1 > p0 ? (uint32_t)((b1 - p0) >> 6) : 0u;
-    uint64_t p = p0;
-    if (nl) {
-        const uint4 *q = (const uint4 *)(bytes + p0);
-        uint4 buf[NL][4];
-#pragma unroll
-        for (int d = 0; d < NL; d++)
-#pragma unroll
-            for (int u = 0; u < 4; u++) buf[d][u] = q[4u * min((uint32_t)d, nl - 1u) + u];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            buf[0][u].x &= st_hmask(h, 16u * u);
-            buf[0][u].y &= st_hmask(h, 16u * u + 4u);
-            buf[0][u].z &= st_hmask(h, 16u * u + 8u);
-            buf[0][u].w &= st_hmask(h, 16u * u + 12u);
-        }
-        for (uint32_t i = 0; i < nl; i += NL) {
-#pragma unroll
-            for (int d = 0; d < NL; d++) {
-                if (i + d < nl) {
-#pragma unroll
-                    for (int u = 0; u < 4; u++) crcz_blk(c, buf[d][u]);
-                    const uint32_t j = min(i + d + NL, nl - 1u);
-#pragma unroll
-                    for (int u = 0; u < 4; u++) buf[d][u] = q[4u * j + u];
-                }
-            }
-        }
-        p = p0 + (uint64_t)nl * 64u;
-    }
-    /* the rest, [p, b1): up to four 16-byte blocks (each starts below b1, so it lies inside the
-     * 16-byte-rounded allocation), bytes below b0 (a frame inside one line) or from b1 on cleared */
-    const uint32_t nr = (uint32_t)((b1 - p + 15u) >> 4);
-    uint4 t[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++) t[i] = i < nr ? *(const uint4 *)(bytes + p + 16u * i) : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++) {
-        if (i < nr) {
-            const int64_t lo = (int64_t)b0 - (int64_t)(p + 16u * i), hi = (int64_t)b1 - (int64_t)(p + 16u * i);
-            const int32_t l32 = (int32_t)max(min(lo, (int64_t)16), (int64_t)0);
-            const int32_t h32 = (int32_t)max(min(hi, (int64_t)16), (int64_t)0);
-            uint4 v = t[i];
-            v.x &= byte_keep(l32, h32, 0);
-            v.y &= byte_keep(l32, h32, 1);
-            v.z &= byte_keep(l32, h32, 2);
-            v.w &= byte_keep(l32, h32, 3);
-            crcz_blk(c, v);
-        }
-    }
-    if (fin) *fin = c;
-    return crcz_zero(c);
-}
-/* The CRC-16 hand-off to the decode tails, 8 words per frame (crcp[8f..8f+7]): r0, r1 |
- * parity << 31 of a prefix, the lines it holds + 1 (0: none), frame_off's low word (a check);
- * the span to the next frame's offset (0: none), the verdict over that span, frame_off's low
- * word.  Written by k_parse (crc_mode 1: the prefix; 2: both). */
-#define CRCP_WORDS 8u
-/* the decode tails' CRC-16 verdict of the frame [b0, b1): the hand-off's verdict when the
- * frame ends where the next one starts, else its prefix continued, else the whole frame */
-DEV bool st_crc16_frame(const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ crcp, uint32_t f, uint64_t b0,
-                        uint64_t b1) {
-    if (crcp) {
-        const u32x4 v = *(const u32x4 *)(crcp + CRCP_WORDS * (uint64_t)f + 4u);
-        if (v.x && v.z == (uint32_t)b0 && b0 + v.x == b1) return v.y != 0u;
-        const u32x4 q = *(const u32x4 *)(crcp + CRCP_WORDS * (uint64_t)f);
-        const uint64_t from = ((b0 >> 6) + q.z - 1u) * 64u;
-        if (q.z && q.w == (uint32_t)b0 && from <= b1)
-            return st_crc16_ok(bytes, b0, b1, CrcZ{q.x, q.y & 0x0FFFFFFFu, q.y >> 31}, from);
-    }
-    return st_crc16_ok(bytes, b0, b1);
-}
 
 /* One step of k_parse's residual walk: up to two Rice codewords of the current partition
  * (parameter k; km = 31 - k, k1 = k + 1).  Two codewords per 32-bit window when both fit:
@@ -1609,7 +761,7 @@ DEV uint32_t wave_skip_residual(WR &r, const SubHdr &h, uint32_t bs, uint64_t li
     return br_pos(r) > limit ? BNF_ST_TRUNC : BNF_ST_OK;
 }
 
-#if BNF_TU == 0
+#ifdef BNF_K_PARSE
 /* =============================================================== k_sync_scan */
 #define SCAN_BYTES_PER_THREAD 16
 #define SCAN_THREADS 256
@@ -1832,98 +984,8 @@ DEV void parse_frame(const uint32_t *__restrict__ words, uint64_t nbytes, const 
     }
 }
 
-#endif /* BNF_TU == 0 */
+#endif /* BNF_K_PARSE */
 
-/* ================================================================== k_decode */
-#define DEC_LANES 64
-#define RP 72 /* row-buffer stride (dwords) between samples: [sample][lane]; 4*RP = 32 mod 64 banks */
-
-struct RS { /* residual reader state */
-    uint32_t verb;   /* 1: VERBATIM raw values of `k` bits */
-    uint32_t k, esc, left, pidx, nparts, psamples, order, plen, pesc, porder;
-};
-
-/* Rice partition header (read_residual_partitioned_rice_ @0x10012da0) */
-template <bool CHECK = true>
-DEV void read_partition(BR &b, RS &s) {
-    const uint32_t kk = br_read<CHECK>(b, s.plen);
-    s.left = (s.porder == 0 || s.pidx > 0) ? s.psamples : s.psamples - s.order;
-    if (kk < s.pesc) {
-        s.k = kk;
-        s.esc = 0;
-    } else {
-        s.k = br_read<CHECK>(b, 5);
-        s.esc = 1;
-    }
-    s.pidx++;
-}
-
-/* One Rice codeword (the block reader @0x10001b30/@0x1001aed0: u = (q << k) | lsb in
- * 32-bit unsigned, zig-zag). */
-template <bool CHECK = true> /* false: the caller made sure the ring holds the word this reads */
-DEV int32_t rice_one(BR &b, uint32_t k, uint64_t limit, uint32_t &trunc, PendW *pw = nullptr) {
-    const uint32_t w = br_peek(b);
-    /* v_ffbh gives ~0u for w == 0, which fails the unsigned test below like any prefix
-     * too long for the window: the slow path then reads it */
-    const uint32_t q0 = ffbh(w);
-    const bool fast = q0 <= 31u - k;
-    uint32_t u = (q0 << k) | __builtin_amdgcn_ubfe(w, 31u - k - q0, k);
-    const bool slow = any_lane(!fast); /* wave-uniform, taken before the advance (stays in SGPRs) */
-    br_adv<CHECK>(b, fast ? q0 + 1u + k : 0u, pw);
-    if (__builtin_expect(slow, 0)) { /* the work is per lane */
-        STAT(b.stats, 3);
-        if (!fast) { /* long unary prefix: read_unary_unsigned, then the k low bits */
-            uint32_t q;
-            if (!br_unary(b, q, limit)) trunc = 1;
-            u = (q << k) | br_read(b, k);
-        }
-    }
-    return (int32_t)((u >> 1) ^ (0u - (u & 1u)));
-}
-
-/* next residual on the fused paths: a new partition's header and escaped (raw) partitions
- * inline behind wave-uniform tests, so a chunk need not lie inside one partition; Rice
- * codewords as rice_one.  An escaped lane issues its pending row write itself. */
-DEV int32_t rice_fused(BR &b, RS &rs, uint64_t limit, uint32_t &trunc, PendW *pw) {
-    /* one landing check per residual: with words wi .. wi+2 in the landed ring, the up to two
-     * partition headers and one value below (<= 49 bits) advance unchecked; only a long
-     * unary prefix (rice_one's slow path) reads on with checks */
-    if (__builtin_expect(any_lane(b.wi + 2u >= b.vendw), 0)) {
-        br_land(b, 2u);
-        b.nx = ring_word(b, b.wi);
-    }
-    const bool np = rs.left == 0;
-    if (__builtin_expect(any_lane(np), 0)) {
-        if (np) {
-            do { /* partition 0 holds no samples when the order equals the partition size */
-                if (rs.pidx < rs.nparts) {
-                    read_partition<false>(b, rs);
-                } else { /* more samples than the partitions carry: a damaged frame */
-                    trunc = 1;
-                    rs.left = 0x7fffffffu;
-                }
-            } while (rs.left == 0);
-        }
-    }
-    rs.left--;
-    if (__builtin_expect(any_lane(rs.esc != 0u), 0)) {
-        if (rs.esc) {
-            if (pw && pw->on) *pw->at = pw->v;
-            if (pw) pw->on = false;
-            return br_read_s<false>(b, rs.k);
-        }
-    }
-    return rice_one<false>(b, rs.k, limit, trunc, pw);
-}
-
-DEV void finish_partitions(BR &b, RS &s) {
-    if (s.verb) return;
-    while (s.pidx < s.nparts) {
-        uint32_t kk = br_read(b, s.plen);
-        if (kk >= s.pesc) br_read(b, 5);
-        s.pidx++;
-    }
-}
 
 /* saturate to int16 (packssdw) / the low 16 bits as int16 (MMX16 history words) */
 DEV int32_t sat16(int32_t x) { return (int32_t)(int16_t)min(max(x, -32768), 32767); }
@@ -2021,119 +1083,8 @@ DEV void restore_chunk(int32_t *row, const int32_t (&c)[W], int32_t (&x)[W], int
     for (uint32_t j = 0; j < (uint32_t)CH; j += W) restore_steps<0, W, NT>(row, c, x, xt, p, n0 + j, nv, j);
 }
 
-/* CRC-16 (poly 0x8005) over bytes [b0, b1), slice-by-8 with the tables in LDS. */
-DEV uint32_t crc16_step8(uint32_t crc, uint32_t w0, uint32_t w1, const lds_u16 *T) {
-    const uint32_t a = w0 ^ (crc << 16);
-    return T[7 * 256 + (a >> 24)] ^ T[6 * 256 + ((a >> 16) & 0xff)] ^ T[5 * 256 + ((a >> 8) & 0xff)] ^
-           T[4 * 256 + (a & 0xff)] ^ T[3 * 256 + (w1 >> 24)] ^ T[2 * 256 + ((w1 >> 16) & 0xff)] ^
-           T[1 * 256 + ((w1 >> 8) & 0xff)] ^ T[w1 & 0xff];
-}
-DEV uint32_t crc16_range(const uint8_t *__restrict__ bytes, uint64_t b0, uint64_t b1, const lds_u16 *T) {
-    uint32_t crc = 0;
-    uint64_t p = b0;
-    while (p < b1 && (p & 15u)) { crc = ((crc << 8) ^ T[((crc >> 8) ^ bytes[p]) & 0xff]) & 0xffff; p++; }
-    const uint4 *q = (const uint4 *)(bytes + p);
-    const uint32_t nq = (uint32_t)((b1 - p) >> 4);
-    uint32_t i = 0;
-    for (; i + 4 <= nq; i += 4) {
-        uint4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) v[u] = q[i + u];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            crc = crc16_step8(crc, __builtin_bswap32(v[u].x), __builtin_bswap32(v[u].y), T);
-            crc = crc16_step8(crc, __builtin_bswap32(v[u].z), __builtin_bswap32(v[u].w), T);
-        }
-    }
-    for (; i < nq; i++) {
-        const uint4 v = q[i];
-        crc = crc16_step8(crc, __builtin_bswap32(v.x), __builtin_bswap32(v.y), T);
-        crc = crc16_step8(crc, __builtin_bswap32(v.z), __builtin_bswap32(v.w), T);
-    }
-    p += (uint64_t)nq * 16u;
-    while (p < b1) { crc = ((crc << 8) ^ T[((crc >> 8) ^ bytes[p]) & 0xff]) & 0xffff; p++; }
-    return crc;
-}
 
-/* a * b mod P over GF(2) (16-bit polynomials) */
-DEV uint32_t gf_mul(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-    for (int i = 15; i >= 0; i--) {
-        r = (r & 0x8000u) ? ((r << 1) ^ 0x8005u) & 0xffffu : (r << 1);
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-/* crc * x^(8*nbytes) mod P: shift a CRC over nbytes appended bytes */
-DEV uint32_t crc16_shift(uint32_t crc, uint64_t nbytes) {
-    for (int j = 0; j < 40 && nbytes; j++, nbytes >>= 1)
-        if (nbytes & 1u) crc = gf_mul(crc, g_crc16_xpow[j]);
-    return crc;
-}
-
-
-/* Wave-cooperative CRC-16 of one byte range (the whole wave, coalesced 1 KB loads).
- * Layout: 16-byte pieces counted back from e = round_up(b1, 16); lane l takes pieces
- * 63 - l + 64 m, so every wave load is 64 consecutive pieces.  Each lane runs a CRC over
- * its own pieces with the 1008 bytes between them as zeros (x^(8*1008) by table TK), the
- * result is shifted to e by lanec = x^(8*16*(63 - l)), and the lanes are XOR-reduced.
- * Returns (wave-uniform) CRC([b0, b1)) * x^(8(e - b1)) mod P: zero iff the range's CRC is
- * zero (x is invertible mod P).  Bytes outside
- * [b0, b1) are masked to 0 (leading zeros leave a zero-initialised CRC at 0). */
-DEV uint32_t crc_mulk(uint32_t a, const lds_u16 *TK) { return TK[a & 0xffu] ^ TK[256u + (a >> 8)]; }
-DEV uint4 gld16(const uint8_t *p) { /* a global (not flat) 16-byte load */
-    const u32x4 v = *(__attribute__((address_space(1))) const u32x4 *)(uintptr_t)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-DEV uint32_t wave_crc_range(const uint8_t *__restrict__ bytes, uint64_t b0, uint64_t b1, const lds_u16 *T,
-                            const lds_u16 *TK, uint32_t lanec, uint32_t lane) {
-    const uint64_t e = (b1 + 15u) & ~15ull, a0 = b0 & ~15ull;
-    const uint32_t np = (uint32_t)((e - a0) >> 4), M = (np + 63u) >> 6;
-    uint32_t acc = 0;
-    for (uint32_t m0 = 0; m0 < M; m0 += 4u) {
-        uint4 v[4];
-        uint64_t pp[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t m = m0 + (uint32_t)u;
-            const uint32_t r = 63u - lane + 64u * (M - 1u - min(m, M - 1u));
-            pp[u] = e - 16ull * (r + 1u);
-            v[u] = (m < M && r < np) ? gld16(bytes + pp[u]) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            if (m0 + (uint32_t)u >= M) break; /* wave-uniform */
-            const int64_t lo = (int64_t)b0 - (int64_t)pp[u], hi = (int64_t)b1 - (int64_t)pp[u];
-            const bool edge = lo > 0 || hi < 16;
-            if (any_lane(edge)) {
-                if (edge) {
-                    const int32_t l32 = (int32_t)max(min(lo, (int64_t)16), (int64_t)0);
-                    const int32_t h32 = (int32_t)max(min(hi, (int64_t)16), (int64_t)0);
-                    v[u].x &= byte_keep(l32, h32, 0);
-                    v[u].y &= byte_keep(l32, h32, 1);
-                    v[u].z &= byte_keep(l32, h32, 2);
-                    v[u].w &= byte_keep(l32, h32, 3);
-                }
-            }
-            acc = crc_mulk(acc, TK);
-            acc = crc16_step8(acc, __builtin_bswap32(v[u].x), __builtin_bswap32(v[u].y), T);
-            acc = crc16_step8(acc, __builtin_bswap32(v[u].z), __builtin_bswap32(v[u].w), T);
-        }
-    }
-    acc = gf_mul(acc, lanec);
-    for (int o = 32; o > 0; o >>= 1) acc ^= (uint32_t)__shfl_xor((int)acc, o);
-    return acc;
-}
-/* the TK table (x^(8*1008) by bytes) into LDS, by the whole wave */
-DEV void crc_tk_fill(lds_u16 *TK, uint32_t lane) {
-    const uint32_t K = crc16_shift(1u, 1008u);
-    for (uint32_t i = lane; i < 256u; i += 64u) {
-        TK[i] = (uint16_t)gf_mul(i, K);
-        TK[256u + i] = (uint16_t)gf_mul(i << 8, K);
-    }
-}
-
-#if BNF_TU == 0
+#ifdef BNF_K_PARSE
 /* ============================================================== k_parse
  * One lane per frame (parse_frame: the lane-serial subframe walk), 64 frames per single-wave
  * workgroup, in the parse order when there is one. */
@@ -2292,17 +1243,6 @@ __global__ void __launch_bounds__(64) k_fill_bad(const bnf_frame_info *__restric
 }
 #endif
 
-/* Channel decorrelation (read_frame_ @0x10011a37-0x10011adb), 32-bit wrap. */
-DEV void decorrelate(uint32_t as, int32_t &v0, int32_t &v1) {
-    if (as == 1) v1 = (int32_t)((uint32_t)v0 - (uint32_t)v1);
-    else if (as == 2) v0 = (int32_t)((uint32_t)v0 + (uint32_t)v1);
-    else if (as == 3) {
-        uint32_t mid = (uint32_t)v0, side = (uint32_t)v1;
-        mid = (mid << 1) | (side & 1u);
-        v0 = (int32_t)(mid + side) >> 1;
-        v1 = (int32_t)(mid - side) >> 1;
-    }
-}
 
 /* Pack one chunk: every lane writes a contiguous run of CH/chn_lanes samples of its own
  * frame (metadata in registers), reading the frame's channel rows from LDS.  Stereo
@@ -3043,7 +1983,7 @@ __global__ void __launch_bounds__(DEC_LANES, 2) k_decode_seg(const uint32_t *__r
     }
 }
 
-#if BNF_TU == 0
+#ifdef BNF_K_PARSE
 /* ============================================================ frame chain (8f-1)
  * Which sync candidates are frames.  libFLAC finds the next frame where the previous one
  * ends (read_frame_ leaves the reader after the CRC-16 footer, frame_sync_ @0x10011760
@@ -3649,9 +2589,9 @@ __global__ void k_ms_status(const uint32_t *__restrict__ ctl, uint32_t cand_cap,
     status[2] = total;
     status[3] = 0u;
 }
-#endif /* BNF_TU == 0 */
+#endif /* BNF_K_PARSE */
 
-#if BNF_TU == 3 || BNF_TU == 4 || BNF_TU == 7 /* TU 7: k_decode_sw, on the same helpers */
+#if defined(BNF_ST_FD) || defined(BNF_K_SW) /* k_decode_sw runs on the same helpers */
 /* =============================================================== k_decode_st
  * Stereo fast path: one lane per 2-channel frame (both subframes, two independent bit
  * cursors), 64 frames per single-wave workgroup.  Same arithmetic as k_decode (read_frame_
@@ -4689,7 +3629,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
     }
 }
 
-#if BNF_TU == 7
+#ifdef BNF_K_SW
 /* ============================================================ k_decode_sw
  * One lane per stereo frame above 16 bits (C3: 96 kHz / 24-bit, M/S, wasted bits, LPC-12),
  * k_decode_st's design with libFLAC's wide restore (lpc_restore_signal_wide @0x10006120):
@@ -5237,49 +4177,20 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
         info[f].flags = fi.flags | BNF_FL_REDO;
     }
 }
-#endif /* BNF_TU == 7 */
-#endif /* BNF_TU == 3 || BNF_TU == 4 || BNF_TU == 7 */
+#endif /* BNF_K_SW */
+#endif /* BNF_ST_FD || BNF_K_SW */
 
 /* ------------------------------------------------------------- host launchers */
-/* The library is built from this file once per BNF_TU (build.py HIP_TUS), so the instances
- * compile in parallel.  Each TU is its own code object with its own __constant__ tables and
- * g_stats: the two functions below act on this TU's copy, and each TU publishes them as its
- * bnf_tu_ops entry (bnflac_launch.h), which TU 0 loops over. */
-static hipError_t tu_upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow) {
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc8_tab), crc8, 256);
-    if (e != hipSuccess) return e;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_crc16_tab), crc16x8, 8 * 256 * sizeof(uint16_t));
-    if (e != hipSuccess) return e;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_crc16_xpow), xpow, 40 * sizeof(uint16_t));
-}
-static hipError_t tu_stats(uint64_t *out16, int reset) { /* adds this TU's g_stats to out16 */
-    uint64_t v[16];
-    hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_stats), sizeof v);
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < 16; i++) out16[i] += v[i];
-    if (reset) {
-        static const uint64_t z[16] = {0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_stats), z, sizeof z);
-    }
-    return e;
-}
-
 /* what this TU holds, as the suffix of its launcher and of its bnf_tu_ops entry */
-#if BNF_TU == 1
+#ifdef BNF_DEC_W
+#if BNF_DEC_W == 8
 #define TU_FN(name) name##_w8
-#elif BNF_TU == 2
-#define TU_FN(name) name##_w32
-#elif BNF_TU == 5
+#elif BNF_DEC_W == 16
 #define TU_FN(name) name##_w16
-#elif BNF_TU == 3
-#define TU_FN(name) name##_st_fd
-#elif BNF_TU == 4
-#define TU_FN(name) name##_st_any
-#elif BNF_TU == 7
-#define TU_FN(name) name##_sw
+#else
+#define TU_FN(name) name##_w32
 #endif
-#if BNF_TU == 1 || BNF_TU == 2 || BNF_TU == 5
-#define DEC_W (BNF_TU == 1 ? 8 : (BNF_TU == 5 ? 16 : 32))
+#define DEC_W BNF_DEC_W
 #define DEC_RD 8 /* ring slots (16 for k_decode<32> measured: LDS then caps it at 6 waves per CU) */
 bnf_tu_ops TU_FN(bnf_ops_decode) = {tu_upload_tables, tu_stats};
 extern "C" {
@@ -5294,7 +4205,7 @@ hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint
                        fmt, out, out_bytes, info, perm, (bnf_ablate_flags() & BNF_ABLATE_K_DECODE) | (mode & BNF_MODE_K_DECODE), seg);
     return hipGetLastError();
 }
-#if BNF_TU == 2
+#if BNF_DEC_W == 32
 /* k_decode_sys's hand-back list (W = 32: every order); nframes bounds the list */
 hipError_t bnf_launch_decode_list(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
                                       uint32_t chn_lanes, int fmt, uint8_t *out, uint64_t out_bytes, bnf_frame_info *info,
@@ -5319,8 +4230,12 @@ hipError_t bnf_launch_decode_seg(const uint32_t *words, uint64_t nbytes, uint32_
 } /* extern "C" */
 #endif
 
-#if BNF_TU == 3 || BNF_TU == 4
-/* TU 3: k_decode_st<FLACDECODER>; TU 4: the other layouts */
+#ifdef BNF_ST_FD /* 1: k_decode_st<FLACDECODER>; 0: the other layouts */
+#if BNF_ST_FD
+#define TU_FN(name) name##_st_fd
+#else
+#define TU_FN(name) name##_st_any
+#endif
 bnf_tu_ops TU_FN(bnf_ops_decode) = {tu_upload_tables, tu_stats};
 extern "C" {
 /* stereo fast path; launched before k_decode<8> (it hands frames back to it) */
@@ -5330,7 +4245,7 @@ hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint
     const dim3 grid((nframes + 63) / 64);
     const uint32_t ab = (bnf_ablate_flags() & BNF_ABLATE_K_DECODE_ST) | (mode & BNF_MODE_K_DECODE_ST);
     if (ab & BNF_ABLATE_NO_ST) return hipSuccess; /* everything to k_decode<8> */
-#if BNF_TU == 3
+#if BNF_ST_FD
     (void)fmt;
     hipLaunchKernelGGL(k_decode_st<BNF_OUT_FLACDECODER>, grid, dim3(64), 0, s, words, nbytes, nframes, sp, chn_lanes, out, out_bytes, info, perm, ab, crcp);
 #else
@@ -5351,8 +4266,8 @@ hipError_t TU_FN(bnf_launch_decode)(const uint32_t *words, uint64_t nbytes, uint
 } /* extern "C" */
 #endif
 
-#if BNF_TU == 7
-bnf_tu_ops TU_FN(bnf_ops_decode) = {tu_upload_tables, tu_stats};
+#ifdef BNF_K_SW
+bnf_tu_ops bnf_ops_decode_sw = {tu_upload_tables, tu_stats};
 extern "C" {
 /* stereo frames above 16 bits; launched before k_decode<8>/<16>/<32> (it hands frames back to k_decode<16>) */
 hipError_t bnf_launch_decode_sw(const uint32_t *words, uint64_t nbytes, uint32_t nframes, bnf_stream_params sp,
@@ -5377,7 +4292,7 @@ hipError_t bnf_launch_decode_sw(const uint32_t *words, uint64_t nbytes, uint32_t
 } /* extern "C" */
 #endif
 
-#if BNF_TU == 0
+#ifdef BNF_K_PARSE
 /* mode switches are read by launching threads while a test or tool may set them: atomics */
 static std::atomic<uint32_t> g_ablate{0xFFFFFFFFu};
 /* every kernel TU but this one (its tables are uploaded first, its g_stats are not reported) */

@@ -1,7 +1,7 @@
 /*
  * bnflac_launch.h -- everything the translation units of libbnflac.so say to each other,
  * declared once: the kernels' `ablate` word, the per-TU table/stats entries, the decode
- * launchers of the kernel TUs and the entry points of TU 0 that bnflac_runtime.cpp
+ * launchers of the kernel TUs and the entry points of the parse TU (-DBNF_K_PARSE) that bnflac_runtime.cpp
  * and bnflac_reader.cpp call.  Every file that defines or calls one of these includes this
  * header, so the compiler checks each definition against its declaration (all of them are
  * extern "C" and hidden: a drifted prototype would still link).
@@ -128,7 +128,7 @@ static_assert(!((BNF_ABLATE_NO_SW | BNF_ABLATE_NO_W8SPLIT) & BNF_MODE_MASK), "a 
 
 /* ------------------------------------------------------------- per-TU tables and counters
  * Each kernel TU is its own code object with its own __constant__ CRC tables and g_stats
- * (bnflac_kernels.hip defines the pair once; every TU instantiates it).  TU 0 keeps the table of
+ * (bnf_common.h defines the pair once; every TU instantiates it).  The parse TU keeps the table of
  * these entries and loops over it in bnf_upload_tables and bnf_stats. */
 typedef struct {
     hipError_t (*upload_tables)(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow);
@@ -140,7 +140,7 @@ extern bnf_tu_ops bnf_ops_decode_w8, bnf_ops_decode_w16, bnf_ops_decode_w32, bnf
     bnf_ops_decode_sw, bnf_ops_decode_sys;
 
 extern "C" {
-/* the user's ablation bits (the one g_ablate, in TU 0) */
+/* the user's ablation bits (the one g_ablate, in the parse TU) */
 uint32_t bnf_ablate_flags(void);
 void bnf_set_ablate(uint32_t v);
 
@@ -166,7 +166,7 @@ hipError_t bnf_launch_decode_sw(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t 
 /* redo: [0] hand-back count (zeroed by the caller), [4..] the frames handed back */
 hipError_t bnf_launch_decode_sys(BNF_DECODE_ARGS, const uint32_t *perm, uint32_t *redo, uint32_t mode, hipStream_t s);
 
-/* ------------------------------------------------------------- TU 0 (parse, index, dispatch): entry points */
+/* ------------------------------------------------------------- the parse TU (parse, index, dispatch): entry points */
 hipError_t bnf_upload_tables(const uint8_t *crc8, const uint16_t *crc16x8, const uint16_t *xpow);
 hipError_t bnf_stats(uint64_t *out16, int reset);
 hipError_t bnf_launch_sync_scan(const uint8_t *d, uint64_t n, uint32_t *d_block_counts, uint32_t *d_total,

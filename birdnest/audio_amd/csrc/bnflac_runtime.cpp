@@ -194,7 +194,7 @@ extern "C" BNFLAC_API int bnflac_ctx_create(int device, bnflac_ctx **out) {
 }
 
 /* Debug: the CRC-16 hand-off of the ctx's last bnflac_parse_frames (8 words per frame, see
- * CRCP_WORDS in bnflac_kernels.hip), synchronously; -1 when there is none for nframes frames */
+ * CRCP_WORDS in bnf_crc16.h), synchronously; -1 when there is none for nframes frames */
 extern "C" BNFLAC_API int bnflac_debug_crc_handoff(bnflac_ctx *ctx, uint32_t *out, uint32_t nframes) {
     if (!ctx || !out) return fail("bnflac_debug_crc_handoff: null argument");
     if (!ctx->crcp_bytes || ctx->crcp_n != nframes) return fail("bnflac_debug_crc_handoff: no hand-off for this batch");

@@ -45,8 +45,9 @@
  * k_decode<32>, BNF_MODE_LIST) then decodes exactly those frames from scratch, so records and
  * bytes equal the lane path's for every frame.
  */
-#define BNF_TU 8
-#include "bnflac_kernels.hip"
+#include "bnf_crc16_tab.h"
+#include "bnf_frame.h"
+#include "bnf_residual.h"
 
 #define SYS_CHK 32                   /* samples per chunk: one s_barrier per chunk */
 #define SYS_RP 80                    /* row stride (dwords), [sample][slot]: 80 = 16 mod 64 banks */

@@ -2,7 +2,7 @@
 and checked against the oracle's bit-serial CRC-16 (oracle/flac_oracle.c, libFLAC's
 FLAC__crc16 @ read_frame_'s footer check, LibFlac.dll@0x10011a01).
 
-- The decode tails' zero test (bnflac_kernels.hip st_crc16_ok / crcz_w / crcz_zero): the CRC of
+- The decode tails' zero test (bnf_crc16.h st_crc16_ok / crcz_w / crcz_zero): the CRC of
   frame + footer is zero iff the message has even parity and is 0 mod T = x^15 + x + 1
   (P = x^16 + x^15 + x^2 + 1 = (x + 1) T), with the remainder kept mod T^4 = x^60 + x^4 + 1 in
   two words, five operations per 32-bit word.
@@ -26,7 +26,7 @@ def bswap(w):
 
 
 def crcz_w(z, le):
-    """bnflac_kernels.hip crcz_w: one little-endian stream word into the T^4 remainder."""
+    """bnf_crc16.h crcz_w: one little-endian stream word into the T^4 remainder."""
     r0, r1, px = z
     w = bswap(le)
     h = ((r1 << 32 | r0) >> 28) & M32  # v_alignbit(r1, r0, 28)

@@ -67,11 +67,14 @@ def _mixed_batch(n_each, class1=False):
     return bytes(data), o, os_, np.concatenate(pcm), base
 
 
-def _decode(data, offs, osmp, total, sp=None):
-    """osmp None: frames positioned by their own sample numbers (a whole stream, sp its STREAMINFO)."""
+def _decode(data, offs, osmp, total, sp=None, fmt=None):
+    """osmp None: frames positioned by their own sample numbers (a whole stream, sp its STREAMINFO).
+    fmt None: OUT_INTERLEAVED32."""
     import torch
     from birdnest.audio_amd import libflac
     dev = torch.device("cuda:0")
+    if fmt is None:
+        fmt = libflac.OUT_INTERLEAVED32
     if sp is None:
         sp = libflac.StreamParams(1, 4096, 4096, 44100, 2, 16, total)
     n = len(data)
@@ -79,11 +82,10 @@ def _decode(data, offs, osmp, total, sp=None):
     d_bytes[:n] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
     d_offs = torch.from_numpy(offs).to(dev)
     d_os = torch.from_numpy(osmp).to(dev) if osmp is not None else None
-    stride = libflac.out_stride(libflac.OUT_INTERLEAVED32, sp)
+    stride = libflac.out_stride(fmt, sp)
     d_out = torch.full((total * stride,), 0xAB, dtype=torch.uint8, device=dev)
     d_info = torch.zeros(len(offs) * libflac.FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
-    libflac.BatchDecoder(0).decode_frames(d_bytes, n, d_offs, len(offs), sp, libflac.OUT_INTERLEAVED32, d_out,
-                                          d_info, d_out_sample=d_os)
+    libflac.BatchDecoder(0).decode_frames(d_bytes, n, d_offs, len(offs), sp, fmt, d_out, d_info, d_out_sample=d_os)
     torch.cuda.synchronize()
     return d_out.cpu().numpy(), libflac.info_array(d_info.cpu().numpy())
 
@@ -169,6 +171,7 @@ def test_w8_split_launches(n_each):
 
 
 FL_W32, FL_ST, FL_W16 = 16, 32, 128
+FL_WAVE_REDO = 512  # BNF_FL_WAVE_REDO: k_decode_sys handed the frame back to k_decode_list
 SYS_ONLY_BITS = 0x40000 | 0x80000  # bnflac_launch.h: BNF_ABLATE_SYS_MIXED | BNF_ABLATE_SYS_LAND_ONLY
 
 
@@ -211,3 +214,59 @@ def test_sys_ablate_bits_never_reach_lane_kernels(batch):
         L.bnflac_debug_set_ablate(0)
     assert info1.tobytes() == info.tobytes()
     assert out1.tobytes() == out.tobytes()
+
+
+def _three_frames(**kw):
+    from birdnest.audio_amd import synth
+    s = synth.encode(synth.config("C2", nframes=3, **kw))
+    fo = s.frame_offsets.astype(np.int64)
+    assert len(fo) == 3
+    return s.data.tobytes(), fo, np.arange(3, dtype=np.int64) * 4096, s.pcm, s.nsamples
+
+
+@pytest.mark.skipif(not gpu_available(), reason="no GPU")
+def test_every_kernel_tu_reports_its_counters():
+    """bnf_stats sums g_stats over the table of kernel TUs that the parse TU keeps (g_tus); a
+    TU left out of it uploads no tables and reports no counters.  One 3-frame batch (a partial
+    wave, a last frame) per counting object -- k_decode_st<FLACDECODER>, k_decode_st's other
+    layouts, k_decode<16>, k_decode<32>, k_decode<8>, k_decode_sys -- with the counters on
+    (BNF_ABLATE_STATS): each must count its waves (slot 5), next to the usual status, CRC and PCM
+    checks.  The flags say which lane kernel a batch went to.  (k_decode_sw has no slot 5.)"""
+    import ctypes
+    from birdnest.audio_amd import libflac, synth
+    L = libflac.load()
+    plain = _three_frames(seed=44)
+    classes = (FL_ST | FL_W16 | FL_W32)
+    cases = [  # name, batch, layout, the class every frame must carry, k_decode_sys
+        ("k_decode_st<FLACDECODER>", plain, libflac.OUT_FLACDECODER, FL_ST, 0),
+        ("k_decode_st<INTERLEAVED32>", plain, libflac.OUT_INTERLEAVED32, FL_ST, 0),
+        ("k_decode<16>", _three_frames(order=12, seed=42), libflac.OUT_INTERLEAVED32, FL_W16, 0),
+        ("k_decode<32>", _three_frames(order=32, partition_order=-1, seed=43), libflac.OUT_INTERLEAVED32, FL_W32, 0),
+        ("k_decode<8>", _three_frames(subframe_mode=synth.SUB_MIXED, seed=45), libflac.OUT_INTERLEAVED32, 0, 0),
+        ("k_decode_sys", plain, libflac.OUT_INTERLEAVED32, FL_ST, 1),
+    ]
+    buf = (ctypes.c_uint64 * 16)()
+    for name, (data, offs, osmp, pcm, total), fmt, cls, sys_on in cases:
+        L.bnflac_debug_stats(buf, 1)
+        L.bnflac_debug_set_ablate(0x100)  # BNF_ABLATE_STATS
+        L.bnflac_debug_set_decode_sys(sys_on)
+        try:
+            out, info = _decode(data, offs, osmp, total, fmt=fmt)
+        finally:
+            L.bnflac_debug_set_decode_sys(0)
+            L.bnflac_debug_set_ablate(0)
+        L.bnflac_debug_stats(buf, 1)
+        assert (info["status"] == 0).all() and (info["crc_ok"] == 1).all(), name
+        if cls:
+            assert ((info["flags"] & classes) == cls).all(), (name, info["flags"])
+        else:  # class 1: at least one frame that no other lane kernel takes
+            assert ((info["flags"] & classes) == 0).any(), (name, info["flags"])
+        if cls == FL_ST and not sys_on:  # k_decode_st kept its frames: the count is its own
+            assert not (info["flags"] & FL_REDO).any(), (name, info["flags"])
+        if sys_on:  # k_decode_sys handed nothing back: no k_decode_list wave (the W = 32 object) counted
+            assert not (info["flags"] & FL_WAVE_REDO).any(), (name, info["flags"])
+        if fmt == libflac.OUT_FLACDECODER:
+            assert out.tobytes() == (pcm.astype(np.int64) & 0xFFFF).astype("<u2").tobytes(), name
+        else:
+            assert np.array_equal(out.view("<i4").reshape(-1, 2), pcm), name
+        assert buf[5] > 0, (name, list(buf))

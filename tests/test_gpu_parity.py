@@ -417,7 +417,7 @@ def test_crc_handoff_contract(gpu, decode_mode, crc_mode):
     assert np.array_equal(decode(d_info), ref)
 
 
-_T15 = (1 << 15) | 3  # T = x^15 + x + 1: P = (x + 1) T (the tails' zero test, bnflac_kernels.hip)
+_T15 = (1 << 15) | 3  # T = x^15 + x + 1: P = (x + 1) T (the tails' zero test, bnf_crc16.h)
 
 
 def _gf2_mod(a: int, m: int) -> int:

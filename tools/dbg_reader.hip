@@ -1,6 +1,6 @@
-// Standalone check of the LDS-ring bit reader (BR in bnflac_kernels.hip) against a plain
+// Standalone check of the LDS-ring bit reader (BR in bnf_bitreader.h) against a plain
 // bit extractor.  Build: hipcc --offload-arch=gfx950 -O3 -I include tools/dbg_reader.hip
-#include "../birdnest/audio_amd/csrc/bnflac_kernels.hip"
+#include "../birdnest/audio_amd/csrc/bnf_bitreader.h"
 #include <cstdio>
 #include <vector>
 
