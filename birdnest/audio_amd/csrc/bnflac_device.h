@@ -74,6 +74,33 @@ typedef struct {
     uint64_t total_samples; /* 0: unknown (no EOS rule) */
 } bnf_stream_desc;
 
+/* Per-stream result of bnflac_scan_streams (== bnflac_stream_meta).  64 bytes. */
+enum {
+    BNF_SCAN_OK = 0,
+    BNF_SCAN_NO_MARKER = 1,
+    BNF_SCAN_TRUNCATED = 2,
+    BNF_SCAN_NO_STREAMINFO = 3,
+    BNF_SCAN_TOO_MANY_BLOCKS = 4,
+    BNF_SCAN_BAD_RANGE = 5
+};
+enum { BNF_SCAN_MAX_BLOCKS = 1024 };
+enum {
+    BNF_META_ID3 = 1u,       /* an ID3v2 tag was skipped */
+    BNF_META_DIFFERS = 2u,   /* STREAMINFO differs from the expected parameters */
+    BNF_META_MD5_ZERO = 4u,  /* STREAMINFO's md5sum is all zero ("not computed") */
+    BNF_META_SEEKTABLE = 8u  /* a SEEKTABLE block was met */
+};
+
+typedef struct {
+    uint32_t status;        /* BNF_SCAN_* */
+    uint32_t flags;         /* BNF_META_* */
+    uint32_t nblocks;       /* metadata block headers read */
+    uint32_t id3_bytes;     /* bytes of the ID3v2 tag in front of the marker */
+    bnf_stream_params sp;   /* has_stream_info 1 when status is OK */
+    uint32_t min_framesize, max_framesize;
+    uint64_t first_offset;  /* absolute; the stream's end when status is not OK */
+} bnf_stream_meta;
+
 /* Device scratch of the batched frame chain (bnf_launch_chain_streams); C = cand_cap,
  * S = nstreams, B = scan workgroups of the buffer (bnf_scan_blocks). */
 typedef struct {

@@ -207,6 +207,15 @@ hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const
 hipError_t bnf_launch_md5_streams(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t unit, uint32_t src,
                                   const uint64_t *bounds, uint32_t nstreams, const uint8_t *expected, uint8_t *md5,
                                   uint32_t *verdict, uint32_t *status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_scan.hip (no tables, no g_stats, no ablate word)
+ * k_scan_streams: the metadata walk (bnf_metadata.h) of the streams sd[0, nstreams) of bytes.
+ * Writes first_offset and total_samples of every sd entry, and one record / 16 md5sum bytes per
+ * stream where meta / md5 are not nullptr.  expect: nullptr, or the parameters a kept stream
+ * has (host memory; copied).  Zeroes status (4 words) on s, then launches. */
+hipError_t bnf_launch_scan_streams(const uint8_t *bytes, uint64_t nbytes, bnf_stream_desc *sd, uint32_t nstreams,
+                                   const bnf_stream_params *expect, bnf_stream_meta *meta, uint8_t *md5,
+                                   uint32_t *status, hipStream_t s);
 } /* extern "C" */
 
 #endif

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../../include/bnflac.h"
+#include "bnf_metadata.h"
 #include "bnflac_device.h"
 #include "bnflac_launch.h"
 #include "bnflac_md5.h"
@@ -470,6 +471,51 @@ extern "C" BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d
                                             d_frame_offsets, d_out_sample, (bnf_frame_info *)d_info, cap, d_stream_frames,
                                             d_stream_samples, d_status, s);
     return e == hipSuccess ? 0 : fail(std::string("bnflac_index_streams: ") + hipGetErrorString(e));
+}
+
+static_assert(sizeof(bnflac_stream_meta) == sizeof(bnf_stream_meta) && sizeof(bnf_stream_meta) == 64, "stream meta layout");
+static_assert(offsetof(bnflac_stream_meta, sp) == 16 && offsetof(bnf_stream_meta, sp) == 16, "stream meta: sp @16");
+static_assert(offsetof(bnflac_stream_meta, min_framesize) == 48 && offsetof(bnf_stream_meta, min_framesize) == 48,
+              "stream meta: min_framesize @48");
+static_assert(offsetof(bnflac_stream_meta, first_offset) == 56 && offsetof(bnf_stream_meta, first_offset) == 56,
+              "stream meta: first_offset @56");
+static_assert(sizeof(bnflac_stream_params) == sizeof(bnf_stream_params), "stream params layout");
+static_assert((int)BNFLAC_SCAN_BAD_RANGE == (int)BNF_SCAN_BAD_RANGE && (int)BNFLAC_SCAN_MAX_BLOCKS == (int)BNF_SCAN_MAX_BLOCKS,
+              "scan status codes");
+
+extern "C" BNFLAC_API int bnflac_scan_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
+                                              bnflac_stream_desc *d_streams, uint32_t nstreams,
+                                              const bnflac_stream_params *expect, bnflac_stream_meta *d_meta,
+                                              uint8_t *d_md5_expected, uint32_t *d_status, void *hs) {
+    if (!ctx) return fail("bnflac_scan_streams: null ctx");
+    DevGuard dg(ctx->device); /* the launch on the context's device */
+    if (!d_status) return fail("bnflac_scan_streams: null d_status");
+    if (nstreams && !d_streams) return fail("bnflac_scan_streams: null descriptor table");
+    if (nbytes && !d_bytes) return fail("bnflac_scan_streams: null d_bytes");
+    if (((uintptr_t)d_bytes) & 15u) return fail("bnflac_scan_streams: d_bytes must be 16-byte aligned");
+    if ((((uintptr_t)d_streams) | ((uintptr_t)d_meta)) & 7u)
+        return fail("bnflac_scan_streams: d_streams and d_meta must be 8-byte aligned");
+    if (((uintptr_t)d_status) & 3u) return fail("bnflac_scan_streams: d_status must be 4-byte aligned");
+    if (nbytes >= (1ull << 34)) return fail("bnflac_scan_streams: buffer larger than 16 GiB");
+    if (nstreams >= (1u << 30)) return fail("bnflac_scan_streams: too many streams");
+    bnf_stream_params x;
+    if (expect) memcpy(&x, expect, sizeof x);
+    hipError_t e = bnf_launch_scan_streams(d_bytes, nbytes, (bnf_stream_desc *)d_streams, nstreams, expect ? &x : nullptr,
+                                           (bnf_stream_meta *)d_meta, d_md5_expected, d_status, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_scan_streams: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_scan_stream_host(const uint8_t *bytes, uint64_t nbytes, bnflac_stream_meta *meta,
+                                                  uint8_t md5[16]) {
+    if (!meta || (nbytes && !bytes)) return fail("bnflac_scan_stream_host: null argument");
+    bnf_stream_meta m;
+    uint64_t first, total;
+    uint32_t sum[4];
+    bnf_metadata_scan(bnf_bytes{bytes}, 0, nbytes, false, nullptr, m, first, total, sum);
+    memcpy(meta, &m, sizeof m);
+    if (md5)
+        for (int i = 0; i < 16; i++) md5[i] = (uint8_t)(sum[i >> 2] >> (8 * (i & 3)));
+    return 0;
 }
 
 /* ====================================================================== */

@@ -127,6 +127,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_out_stride", "bnflac_debug_set_ablate", "bnflac_debug_stats", "bnflac_debug_set_parse_wave", "bnflac_debug_parse_wave_stats",
                  "bnflac_debug_set_decode_sys", "bnflac_debug_decode_seg_launches", "bnflac_md5_interleaved32", "bnflac_index_stream",
                  "bnflac_index_streams", "bnflac_md5_layout", "bnflac_md5_streams",
+                 "bnflac_scan_streams", "bnflac_scan_stream_host",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -215,6 +216,10 @@ def load() -> ctypes.CDLL:
     L.bnflac_md5_layout.restype, L.bnflac_md5_layout.argtypes = ctypes.c_uint32, [i, p]
     L.bnflac_md5_streams.restype = i
     L.bnflac_md5_streams.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, p, p, p, p, p]
+    L.bnflac_scan_streams.restype = i
+    L.bnflac_scan_streams.argtypes = [p, p, ctypes.c_uint64, p, ctypes.c_uint32, p, p, p, p, p]
+    L.bnflac_scan_stream_host.restype = i
+    L.bnflac_scan_stream_host.argtypes = [p, ctypes.c_uint64, p, p]
     _LIB = L
     return L
 
@@ -334,6 +339,44 @@ STREAM_DESC_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("first_offset",
 assert STREAM_DESC_DTYPE.itemsize == ctypes.sizeof(StreamDesc)
 
 
+SCAN_OK, SCAN_NO_MARKER, SCAN_TRUNCATED, SCAN_NO_STREAMINFO, SCAN_TOO_MANY_BLOCKS, SCAN_BAD_RANGE = range(6)
+SCAN_MAX_BLOCKS = 1024
+# StreamMeta.flags
+META_ID3, META_DIFFERS, META_MD5_ZERO, META_SEEKTABLE = 1, 2, 4, 8
+
+
+class StreamMeta(ctypes.Structure):
+    """bnflac_stream_meta: one stream's record of scan_streams / scan_stream_host."""
+    _fields_ = [("status", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("nblocks", ctypes.c_uint32),
+                ("id3_bytes", ctypes.c_uint32), ("sp", StreamParams), ("min_framesize", ctypes.c_uint32),
+                ("max_framesize", ctypes.c_uint32), ("first_offset", ctypes.c_uint64)]
+
+
+STREAM_META_BYTES = 64
+STREAM_META_DTYPE = np.dtype([
+    ("status", "<u4"), ("flags", "<u4"), ("nblocks", "<u4"), ("id3_bytes", "<u4"), ("has_stream_info", "<i4"),
+    ("min_blocksize", "<u4"), ("max_blocksize", "<u4"), ("sample_rate", "<u4"), ("channels", "<u4"), ("bps", "<u4"),
+    ("total_samples", "<u8"), ("min_framesize", "<u4"), ("max_framesize", "<u4"), ("first_offset", "<u8")])
+assert STREAM_META_DTYPE.itemsize == ctypes.sizeof(StreamMeta) == STREAM_META_BYTES
+
+
+def scan_stream_host(data):
+    """The metadata walk of scan_streams over one stream in host memory (bnflac_scan_stream_host,
+    no GPU) -> (StreamMeta, the 16 md5sum bytes; zeros unless the record's status is SCAN_OK)."""
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    meta = StreamMeta()
+    md5 = (ctypes.c_uint8 * 16)()
+    rc = load().bnflac_scan_stream_host(a.ctypes.data if a.size else None, a.size, ctypes.byref(meta), md5)
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return meta, bytes(md5)
+
+
+def meta_array(raw: np.ndarray) -> np.ndarray:
+    """View a uint8 buffer of scan_streams records as a structured array."""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=STREAM_META_DTYPE)
+
+
 def stream_table(streams, nbytes: int) -> np.ndarray:
     """The descriptor table of index_streams from [(begin, end, first_offset, total_samples)],
     checked as the library checks it (its status bit 2): ValueError for a range that is
@@ -440,17 +483,23 @@ class BatchDecoder:
 
     def index_streams(self, d_bytes, nbytes: int, streams, sp: StreamParams, cap: int, cand_cap: int = 0, stream=None):
         """Frame chains of many streams held in one buffer (bnflac_index_streams), one call.
-        streams: [(begin, end, first_offset, total_samples)], ascending and non-overlapping.
+        streams: [(begin, end, first_offset, total_samples)], ascending and non-overlapping, or the
+        same table on the device (int64, 4 words per stream: what scan_streams returns).
         -> (d_offsets int64[cap], d_out_sample int64[cap], d_info uint8[cap*128],
             d_stream_frames int32[n+1], d_stream_samples int64[n+1], d_status int32[4]),
         all on the device and not synchronised: the caller does that, as for decode_parsed."""
         import torch
-        table = stream_table(streams, nbytes)
         dev = d_bytes.device
         s = stream if stream is not None else torch.cuda.current_stream()
-        n = len(table)
+        on_device = isinstance(streams, torch.Tensor)
+        if on_device:  # scan_streams' table: checked by the library (status bit 2), never read here
+            d_tab, n = self._device_table(streams)
+        else:
+            table = stream_table(streams, nbytes)
+            n = len(table)
         with torch.cuda.stream(s):
-            d_tab = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev) if n else None
+            if not on_device:
+                d_tab = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev) if n else None
             d_offs = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
             d_os = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
             d_info = torch.zeros(max(cap, 1) * FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
@@ -466,6 +515,48 @@ class BatchDecoder:
         if rc != 0:
             raise RuntimeError(self.L.bnflac_last_error().decode())
         return d_offs, d_os, d_info, d_sf, d_ss, d_status
+
+    @staticmethod
+    def _device_table(t):
+        """A descriptor table already on the device: 4 64-bit words per stream -> (tensor, nstreams)"""
+        if not t.is_cuda or t.element_size() != 8 or t.numel() % 4 or not t.is_contiguous():
+            raise ValueError("a device stream table is a contiguous CUDA tensor of 4 64-bit words per stream")
+        return t, t.numel() // 4
+
+    def scan_streams(self, d_bytes, nbytes: int, ranges, expect: Optional[StreamParams] = None, stream=None):
+        """The metadata of many streams held in one buffer, read on the device (bnflac_scan_streams).
+        ranges: [(begin, end)], ascending and non-overlapping, or a device table (int64, 4 words per
+        stream, begin and end filled in), which is completed in place and returned.
+        expect: the parameters every kept stream has (a stream with others is emptied), or None.
+        -> (d_table int64[n*4] ready for index_streams, d_meta uint8[n*64], d_md5 uint8[n, 16] ready
+            as md5_streams' d_expected, d_status int32[4]), all on the device and not synchronised,
+        like index_streams."""
+        import torch
+        dev = d_bytes.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        on_device = isinstance(ranges, torch.Tensor)
+        if on_device:
+            d_tab, n = self._device_table(ranges)
+        else:
+            n = len(ranges)
+            table = np.zeros(n, dtype=STREAM_DESC_DTYPE)
+            for k, (begin, end) in enumerate(ranges):
+                table[k] = (begin, end, 0, 0)
+        with torch.cuda.stream(s):
+            if not on_device:
+                d_tab = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev)
+            d_meta = torch.zeros(n * STREAM_META_BYTES, dtype=torch.uint8, device=dev)
+            d_md5 = torch.zeros((n, 16), dtype=torch.uint8, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        rc = self.L.bnflac_scan_streams(self.ctx, ctypes.c_void_p(d_bytes.data_ptr()), nbytes,
+                                        ctypes.c_void_p(d_tab.data_ptr()) if n else None, n,
+                                        ctypes.byref(expect) if expect is not None else None,
+                                        ctypes.c_void_p(d_meta.data_ptr()) if n else None,
+                                        ctypes.c_void_p(d_md5.data_ptr()) if n else None,
+                                        ctypes.c_void_p(d_status.data_ptr()), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_tab, d_meta, d_md5, d_status
 
     def decode_frames(self, d_bytes, nbytes: int, d_offsets, nframes: int, sp: StreamParams, fmt: int, d_out,
                       d_info, d_out_sample=None, base_sample: int = 0, stream=None, out_bytes=None):

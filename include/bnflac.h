@@ -10,7 +10,11 @@
  * machine replay run on the host.
  *
  * Part 2: a batched, device-pointer API (bnflac_*) for callers that keep compressed
- * frames and PCM resident in HBM -- the path bench.py measures.
+ * frames and PCM resident in HBM -- the path bench.py measures.  Whole .flac files in one
+ * buffer go through it without the host reading anything back: bnflac_scan_streams (metadata)
+ * -> bnflac_index_streams (frames) -> bnflac_parse_frames / bnflac_decode_parsed (PCM) ->
+ * bnflac_md5_streams (verification), each asynchronous on the caller's HIP stream and chained by
+ * device tables.
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -157,6 +161,72 @@ typedef struct {
     uint64_t first_offset;  /* absolute offset in d_bytes of the byte after the metadata blocks */
     uint64_t total_samples; /* STREAMINFO total for the end-of-stream rule; 0 = unknown (no rule) */
 } bnflac_stream_desc;
+
+/* Status of one stream of bnflac_scan_streams: the first failure of its walk, in this order. */
+enum {
+    BNFLAC_SCAN_OK = 0,
+    BNFLAC_SCAN_NO_MARKER = 1,       /* no "fLaC" at byte 0 or right after one ID3v2 tag */
+    BNFLAC_SCAN_TRUNCATED = 2,       /* the tag, a block header, STREAMINFO or a block runs past the stream's end */
+    BNFLAC_SCAN_NO_STREAMINFO = 3,   /* none before the last block, or one shorter than 34 bytes */
+    BNFLAC_SCAN_TOO_MANY_BLOCKS = 4, /* no last-block flag within BNFLAC_SCAN_MAX_BLOCKS blocks */
+    BNFLAC_SCAN_BAD_RANGE = 5        /* begin > end, end > nbytes, or begin below the previous entry's end */
+};
+enum { BNFLAC_SCAN_MAX_BLOCKS = 1024 };
+
+/* Per-stream result record (64 bytes), device-resident. */
+typedef struct {
+    uint32_t status;      /* BNFLAC_SCAN_* */
+    uint32_t flags;       /* bit 0 ID3v2 tag skipped, bit 1 STREAMINFO differs from the expected sp,
+                             bit 2 md5sum all zero, bit 3 a SEEKTABLE block was met */
+    uint32_t nblocks;     /* metadata block headers read */
+    uint32_t id3_bytes;   /* bytes of the ID3v2 tag in front of the marker (0: none) */
+    bnflac_stream_params sp;   /* offset 16; has_stream_info 1 when status is OK */
+    uint32_t min_framesize, max_framesize;  /* offset 48 */
+    uint64_t first_offset;     /* offset 56; absolute, as in bnflac_stream_desc */
+} bnflac_stream_meta;
+
+/* The metadata of every stream of a batch, read on the device: the first link of the chain
+ * scan -> bnflac_index_streams -> parse / decode -> bnflac_md5_streams, none of which needs the
+ * host to read anything back.  d_bytes as for bnflac_index_streams (16-byte aligned, allocation
+ * >= round_up(nbytes, 16)).  d_streams is in/out: the caller fills begin and end of every entry
+ * (ascending, non-overlapping; never written), the call writes first_offset and total_samples.
+ * Per stream, over its bytes b[0, n), n = end - begin, the first failure deciding the status:
+ *   a bad range (BAD_RANGE, nothing read); one optional ID3v2 tag at b[0] (libFLAC's
+ *   skip_id3v2_tag_: 10 bytes + the 4 x 7-bit size; flags bit 0); "fLaC" exactly there
+ *   (NO_MARKER); then blocks until the one with the last flag: header (TRUNCATED when cut;
+ *   TOO_MANY_BLOCKS at BNFLAC_SCAN_MAX_BLOCKS), type 0 = STREAMINFO of at least 34 bytes
+ *   (NO_STREAMINFO when shorter; a later one overwrites an earlier one; bytes past 34 skipped),
+ *   type 3 sets flags bit 3, every type skipped by its length (TRUNCATED past the end).  No
+ *   STREAMINFO met: NO_STREAMINFO.  Else OK, first_offset = begin + the bytes walked (== end: a
+ *   stream of no frames).
+ * libFLAC's find_metadata_ also searches junk byte by byte for the marker or a frame sync and
+ * reports LOST_SYNC on the way; such streams are NO_MARKER here and belong to the stream API
+ * (part 1).  Where this walk says OK, libFLAC reaches its first frame at the same offset with
+ * the same STREAMINFO and no error event.
+ * An OK stream is kept when expect is NULL or equals its STREAMINFO in min_blocksize,
+ * max_blocksize, sample_rate, channels and bps: its descriptor gets first_offset and
+ * STREAMINFO's total_samples, d_md5_expected (may be NULL; 16 bytes per stream) the md5sum, flags
+ * bit 2 tells an all-zero one.  Every other stream is emptied: first_offset = end, total_samples
+ * 0, md5sum zeros, so bnflac_index_streams yields no frame for it and bnflac_md5_streams verdict
+ * 2, and stream positions in every later table stay those of the input.  An OK stream that
+ * differs from expect has flags bit 1 and its own values (first_offset too) in its record; a
+ * stream that is not OK has a record of zeros apart from status, flags, nblocks, id3_bytes and
+ * first_offset = end.  d_meta may be NULL.
+ * d_status (device, 4 words): [0] bit 0 some stream not OK, bit 1 some stream differs from
+ * expect, bit 2 some BAD_RANGE; [1] streams kept; [2] streams not OK; [3] streams differing.
+ * nstreams == 0 writes a zero status.  No byte at or past round_up(nbytes, 16) is read, and no
+ * result depends on a byte outside [begin, end).  Asynchronous on hip_stream, no host
+ * synchronisation. */
+BNFLAC_API int bnflac_scan_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
+                                   bnflac_stream_desc *d_streams, uint32_t nstreams,
+                                   const bnflac_stream_params *expect, bnflac_stream_meta *d_meta,
+                                   uint8_t *d_md5_expected, uint32_t *d_status, void *hip_stream);
+
+/* The same walk for one stream in host memory (begin 0, end nbytes, no expected parameters); no
+ * GPU needed.  md5 (may be NULL) receives STREAMINFO's md5sum, zeros when meta->status is not
+ * OK.  0, or -1 for a null meta or bytes. */
+BNFLAC_API int bnflac_scan_stream_host(const uint8_t *bytes, uint64_t nbytes, bnflac_stream_meta *meta,
+                                       uint8_t md5[16]);
 
 /* bnflac_index_stream for many streams held in one buffer, in one call and with no host
  * synchronisation.  Stream s contributes exactly the frames bnflac_index_stream returns for
