@@ -1,0 +1,186 @@
+/*
+ * bnf_select.h -- the rule of bnflac_select_ranges: which frames of a stream a sample window
+ * needs, and what the window looks like in the compact PCM those frames decode into.  One
+ * function over the index's tables, callable from host and device: k_sel_streams
+ * (bnflac_select.hip, one lane per stream) and bnflac_select_ranges_host (bnflac_runtime.cpp)
+ * are the same code, as bnf_metadata.h is for the scan.  The header needs no HIP: a plain C++
+ * compiler takes it too (tools/select_ranges_sanitize.cpp builds it with the sanitizers).
+ *
+ * Stream s, T = its samples, frame i of [f0, f1) at local start L_i = out_sample_i - s0 with
+ * blocksize b_i:  lo = min(first_sample, T), hi = min(lo + nsamples, T) (saturating);
+ * hi == lo: empty.  Else the frames with L_i < hi and L_i + b_i > lo, found by two binary
+ * searches: a = the first frame with L_i + b_i > lo, b = the first frame of [a, f1) with
+ * L_i >= hi.  Both predicates are monotone over the tables bnflac_index_streams writes (L_i
+ * ascends, the frames tile [0, T)), so [a, b) is the contiguous run the rule names.  Over any
+ * other contents the searches still halve an interval of [f0, f1): at most 32 steps each, every
+ * index read inside the stream's range, and a run that comes out empty is an empty window.  All
+ * sample arithmetic is modulo 2^64, so such contents give some window, never a fault.
+ */
+#ifndef BNF_SELECT_H
+#define BNF_SELECT_H
+
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define BNF_SEL_HD __host__ __device__
+#else
+#define BNF_SEL_HD
+#endif
+
+#include "bnflac_device.h"
+
+/* == bnflac_sample_range, bnflac_window (include/bnflac.h) */
+typedef struct {
+    uint64_t first_sample, nsamples;
+} bnf_sample_range;
+
+typedef struct {
+    uint64_t pcm_first;
+    uint64_t nsamples;
+    uint32_t skip, first_frame, nframes, flags;
+} bnf_window;
+
+enum { BNF_WIN_CLIPPED = 1u, BNF_WIN_EMPTY = 2u };          /* bnf_window.flags */
+enum { BNF_SEL_OVERFLOW = 1u, BNF_SEL_BAD_TABLES = 2u };    /* status word 0 */
+
+/* One stream's selection before the prefixes over the streams are known. */
+typedef struct {
+    uint64_t nsamples; /* of the window, clipped */
+    uint64_t hull;     /* samples of the selected frames: the stream's share of the compact PCM */
+    uint32_t skip, first_frame, nframes, flags;
+} bnf_sel_stream;
+
+BNF_SEL_HD inline uint64_t bnf_sel_sat_add(uint64_t a, uint64_t b) {
+    const uint64_t s = a + b;
+    return s < a ? ~(uint64_t)0 : s;
+}
+
+/* Stream s's slice of the index's tables can be searched: ascending, and nothing at or past cap. */
+BNF_SEL_HD inline bool bnf_select_tables_ok(uint32_t f0, uint32_t f1, uint64_t s0, uint64_t s1, uint32_t cap) {
+    return f0 <= f1 && f1 <= cap && s0 <= s1;
+}
+
+/* The rule for one stream whose tables are ok: frames [f0, f1) of info, samples [s0, s1). */
+BNF_SEL_HD inline void bnf_select_stream(const bnf_frame_info *info, uint32_t f0, uint32_t f1, uint64_t s0, uint64_t s1,
+                                         bnf_sample_range r, bnf_sel_stream &o) {
+    const uint64_t T = s1 - s0;
+    const uint64_t lo = r.first_sample < T ? r.first_sample : T;
+    const uint64_t end = bnf_sel_sat_add(lo, r.nsamples);
+    const uint64_t hi = end < T ? end : T;
+    o.nsamples = o.hull = 0;
+    o.skip = 0;
+    o.first_frame = f0;
+    o.nframes = 0;
+    o.flags = bnf_sel_sat_add(r.first_sample, r.nsamples) > T ? BNF_WIN_CLIPPED : 0u;
+    if (hi == lo) {
+        o.flags |= BNF_WIN_EMPTY;
+        return;
+    }
+    uint32_t a = f0, n = f1 - f0; /* the first frame with L_i + b_i > lo */
+    while (n) {
+        const uint32_t h = n >> 1, m = a + h;
+        if (info[m].out_sample - s0 + info[m].blocksize > lo) {
+            n = h;
+        } else {
+            a = m + 1;
+            n -= h + 1;
+        }
+    }
+    uint32_t b = a; /* the first frame of [a, f1) with L_i >= hi */
+    n = f1 - a;
+    while (n) {
+        const uint32_t h = n >> 1, m = b + h;
+        if (info[m].out_sample - s0 >= hi) {
+            n = h;
+        } else {
+            b = m + 1;
+            n -= h + 1;
+        }
+    }
+    if (b == a) { /* only over tables the index did not write */
+        o.flags |= BNF_WIN_EMPTY;
+        return;
+    }
+    const uint64_t first = info[a].out_sample;
+    o.nsamples = hi - lo;
+    o.hull = info[b - 1].out_sample + info[b - 1].blocksize - first;
+    o.skip = (uint32_t)(lo - (first - s0));
+    o.first_frame = a;
+    o.nframes = b - a;
+}
+
+/* The window record of stream s once its prefix in the compact PCM is known. */
+BNF_SEL_HD inline bnf_window bnf_select_window(const bnf_sel_stream &o, uint64_t sel_samples) {
+    bnf_window w;
+    w.pcm_first = sel_samples + o.skip;
+    w.nsamples = o.nsamples;
+    w.skip = o.skip;
+    w.first_frame = o.first_frame;
+    w.nframes = o.nframes;
+    w.flags = o.flags;
+    return w;
+}
+
+/* The window of every stream when the tables are unusable. */
+BNF_SEL_HD inline bnf_window bnf_select_no_window(uint32_t f0) {
+    bnf_window w;
+    w.pcm_first = w.nsamples = 0;
+    w.skip = 0;
+    w.first_frame = f0;
+    w.nframes = 0;
+    w.flags = BNF_WIN_EMPTY;
+    return w;
+}
+
+/* The whole call on host tables: what the three kernels of bnflac_select.hip compute.  offsets and
+ * sel_offsets may be NULL. */
+inline void bnf_select_ranges_host(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
+                                   const uint32_t *stream_frames, const uint64_t *stream_samples, uint32_t nstreams,
+                                   const bnf_sample_range *ranges, uint64_t *sel_offsets, bnf_frame_info *sel_info,
+                                   uint32_t sel_cap, uint32_t *sel_frames, uint64_t *sel_samples, bnf_window *windows,
+                                   uint32_t status[4]) {
+    bool bad = false;
+    for (uint32_t s = 0; s < nstreams; s++)
+        bad = bad || !bnf_select_tables_ok(stream_frames[s], stream_frames[s + 1], stream_samples[s], stream_samples[s + 1], cap);
+    uint32_t nf = 0, nonempty = 0, clipped = 0;
+    uint64_t ns = 0;
+    for (uint32_t s = 0; s < nstreams; s++) {
+        sel_frames[s] = nf;
+        sel_samples[s] = ns;
+        if (bad) {
+            windows[s] = bnf_select_no_window(stream_frames[s]);
+            continue;
+        }
+        bnf_sel_stream o;
+        bnf_select_stream(info, stream_frames[s], stream_frames[s + 1], stream_samples[s], stream_samples[s + 1], ranges[s], o);
+        windows[s] = bnf_select_window(o, ns);
+        const uint64_t first = o.nframes ? info[o.first_frame].out_sample : 0;
+        for (uint32_t k = 0; k < o.nframes; k++) {
+            const uint64_t p = (uint64_t)nf + k;
+            if (p >= sel_cap) break;
+            sel_info[p] = info[o.first_frame + k];
+            sel_info[p].out_sample = ns + (info[o.first_frame + k].out_sample - first);
+            if (sel_offsets) sel_offsets[p] = offsets ? offsets[o.first_frame + k] : 0;
+        }
+        nf += o.nframes;
+        ns += o.hull;
+        nonempty += (o.flags & BNF_WIN_EMPTY) ? 0u : 1u;
+        clipped += (o.flags & BNF_WIN_CLIPPED) ? 1u : 0u;
+    }
+    sel_frames[nstreams] = nf;
+    sel_samples[nstreams] = ns;
+    for (uint32_t p = nf; p < sel_cap; p++) { /* filler: zeros, skipped, no error */
+        memset(&sel_info[p], 0, sizeof sel_info[p]);
+        sel_info[p].status = BNF_ST_SKIPPED;
+        sel_info[p].err = -1;
+        if (sel_offsets) sel_offsets[p] = 0;
+    }
+    status[0] = bad ? BNF_SEL_BAD_TABLES : nf > sel_cap ? BNF_SEL_OVERFLOW : 0u;
+    status[1] = nf;
+    status[2] = nonempty;
+    status[3] = clipped;
+}
+
+#endif

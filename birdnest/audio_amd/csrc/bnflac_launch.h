@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bnf_select.h"
 #include "bnflac_device.h"
 
 /* ------------------------------------------------------------- the `ablate` word
@@ -216,6 +217,24 @@ hipError_t bnf_launch_md5_streams(const uint8_t *pcm, uint64_t pcm_bytes, uint32
 hipError_t bnf_launch_scan_streams(const uint8_t *bytes, uint64_t nbytes, bnf_stream_desc *sd, uint32_t nstreams,
                                    const bnf_stream_params *expect, bnf_stream_meta *meta, uint8_t *md5,
                                    uint32_t *status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_select.hip (no tables, no g_stats, no ablate word)
+ * k_sel_*: the rule of bnf_select.h over the tables of bnf_launch_chain_streams (offsets and
+ * sel_offsets may be nullptr; info and sel_info 16-byte aligned).  scratch: device memory of
+ * bnf_select_scratch_bytes(nstreams) bytes, 16-byte aligned.  Writes every status word. */
+uint64_t bnf_select_scratch_bytes(uint32_t nstreams);
+hipError_t bnf_launch_select_ranges(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap, const uint32_t *sf,
+                                    const uint64_t *ss, uint32_t nstreams, const bnf_sample_range *ranges,
+                                    uint64_t *sel_offsets, bnf_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames,
+                                    uint64_t *sel_samples, bnf_window *windows, uint32_t *status, void *scratch,
+                                    hipStream_t s);
+/* k_gather_ranges: row s = rows + s * row_bytes gets min(windows[s].nsamples, row_samples) sample
+ * frames of `stride` bytes from pcm + windows[s].pcm_first * stride, then zeros up to row_samples
+ * frames.  pcm 16-byte aligned, its allocation at least round_up(pcm_bytes, 16) bytes.  Zeroes
+ * status (4 words) on s, then launches. */
+hipError_t bnf_launch_gather_ranges(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, const bnf_window *windows,
+                                    uint32_t nstreams, uint32_t row_samples, uint64_t row_bytes, uint8_t *rows,
+                                    uint32_t *status, hipStream_t s);
 } /* extern "C" */
 
 #endif

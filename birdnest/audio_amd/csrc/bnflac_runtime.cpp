@@ -172,6 +172,7 @@ struct bnflac_ctx {
     /* bnflac_index_stream scratch */
     CtxBuf cand, info, gap, jump, mark, pos, bs, small;
     CtxBuf ms; /* bnflac_index_streams scratch (bnf_ms_scratch, one allocation) */
+    CtxBuf sel; /* bnflac_select_ranges scratch (flags and workgroup sums) */
     CtxBuf order, porder; /* decode / parse order: histogram + permutation (k_order_*) */
     /* k_parse's CRC-16 hand-off of the last bnflac_parse_frames batch (8 words per frame), and
      * the batch they belong to: bnflac_decode_parsed uses them only for that same batch */
@@ -209,7 +210,7 @@ extern "C" BNFLAC_API void bnflac_ctx_destroy(bnflac_ctx *ctx) {
     if (!ctx) return;
     if (ctx->d_block_counts) (void)hipFree(ctx->d_block_counts);
     for (CtxBuf *b : {&ctx->cand, &ctx->info, &ctx->gap, &ctx->jump, &ctx->mark, &ctx->pos, &ctx->bs, &ctx->small,
-                      &ctx->ms, &ctx->order, &ctx->porder, &ctx->crcp})
+                      &ctx->ms, &ctx->sel, &ctx->order, &ctx->porder, &ctx->crcp})
         b->release();
     delete ctx;
 }
@@ -516,6 +517,88 @@ extern "C" BNFLAC_API int bnflac_scan_stream_host(const uint8_t *bytes, uint64_t
     if (md5)
         for (int i = 0; i < 16; i++) md5[i] = (uint8_t)(sum[i >> 2] >> (8 * (i & 3)));
     return 0;
+}
+
+static_assert(sizeof(bnflac_sample_range) == sizeof(bnf_sample_range) && sizeof(bnf_sample_range) == 16, "sample range layout");
+static_assert(sizeof(bnflac_window) == sizeof(bnf_window) && sizeof(bnf_window) == 32, "window layout");
+static_assert(offsetof(bnflac_window, skip) == 16 && offsetof(bnf_window, skip) == 16 &&
+                  offsetof(bnflac_window, flags) == 28 && offsetof(bnf_window, flags) == 28,
+              "window: skip @16, flags @28");
+static_assert(sizeof(bnflac_frame_info) == sizeof(bnf_frame_info) && sizeof(bnf_frame_info) == 128 &&
+                  offsetof(bnf_frame_info, out_sample) == 64,
+              "frame record: 128 bytes, out_sample @64");
+
+extern "C" BNFLAC_API int bnflac_select_ranges(bnflac_ctx *ctx, const uint64_t *d_frame_offsets,
+                                               const bnflac_frame_info *d_info, uint32_t cap,
+                                               const uint32_t *d_stream_frames, const uint64_t *d_stream_samples,
+                                               uint32_t nstreams, const bnflac_sample_range *d_ranges,
+                                               uint64_t *d_sel_offsets, bnflac_frame_info *d_sel_info, uint32_t sel_cap,
+                                               uint32_t *d_sel_frames, uint64_t *d_sel_samples, bnflac_window *d_windows,
+                                               uint32_t *d_status, void *hs) {
+    if (!ctx) return fail("bnflac_select_ranges: null ctx");
+    DevGuard dg(ctx->device); /* launches and scratch on the context's device */
+    if (!d_status || !d_sel_frames || !d_sel_samples || (sel_cap && !d_sel_info))
+        return fail("bnflac_select_ranges: null output");
+    if (nstreams && (!d_stream_frames || !d_stream_samples || !d_ranges || !d_windows))
+        return fail("bnflac_select_ranges: null table");
+    if (cap && nstreams && !d_info) return fail("bnflac_select_ranges: null d_info");
+    if (d_sel_offsets && cap && nstreams && !d_frame_offsets)
+        return fail("bnflac_select_ranges: d_sel_offsets without d_frame_offsets");
+    if ((((uintptr_t)d_info) | ((uintptr_t)d_sel_info)) & 15u)
+        return fail("bnflac_select_ranges: d_info and d_sel_info must be 16-byte aligned");
+    if ((((uintptr_t)d_frame_offsets) | ((uintptr_t)d_stream_samples) | ((uintptr_t)d_ranges) | ((uintptr_t)d_sel_offsets) |
+         ((uintptr_t)d_sel_samples) | ((uintptr_t)d_windows)) & 7u)
+        return fail("bnflac_select_ranges: the 64-bit tables must be 8-byte aligned");
+    if ((((uintptr_t)d_stream_frames) | ((uintptr_t)d_sel_frames) | ((uintptr_t)d_status)) & 3u)
+        return fail("bnflac_select_ranges: the 32-bit tables must be 4-byte aligned");
+    if (nstreams >= (1u << 30)) return fail("bnflac_select_ranges: too many streams");
+    /* a floor of 4 KiB: batches of up to 340,000 streams never grow it again */
+    if (!ctx->sel.grow(std::max<size_t>((size_t)bnf_select_scratch_bytes(nstreams), 4096)))
+        return fail("bnflac_select_ranges: out of device memory");
+    hipError_t e = bnf_launch_select_ranges(d_frame_offsets, (const bnf_frame_info *)d_info, cap, d_stream_frames,
+                                            d_stream_samples, nstreams, (const bnf_sample_range *)d_ranges, d_sel_offsets,
+                                            (bnf_frame_info *)d_sel_info, sel_cap, d_sel_frames, d_sel_samples,
+                                            (bnf_window *)d_windows, d_status, ctx->sel.p, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_select_ranges: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_select_ranges_host(const bnflac_frame_info *info, uint32_t cap,
+                                                    const uint32_t *stream_frames, const uint64_t *stream_samples,
+                                                    uint32_t nstreams, const bnflac_sample_range *ranges,
+                                                    bnflac_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames,
+                                                    uint64_t *sel_samples, bnflac_window *windows, uint32_t status[4]) {
+    if (!status || !sel_frames || !sel_samples || (sel_cap && !sel_info))
+        return fail("bnflac_select_ranges_host: null output");
+    if (nstreams && (!stream_frames || !stream_samples || !ranges || !windows))
+        return fail("bnflac_select_ranges_host: null table");
+    if (cap && nstreams && !info) return fail("bnflac_select_ranges_host: null info");
+    bnf_select_ranges_host(nullptr, (const bnf_frame_info *)info, cap, stream_frames, stream_samples, nstreams,
+                           (const bnf_sample_range *)ranges, nullptr, (bnf_frame_info *)sel_info, sel_cap, sel_frames,
+                           sel_samples, (bnf_window *)windows, status);
+    return 0;
+}
+
+extern "C" BNFLAC_API int bnflac_gather_ranges(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
+                                               const bnflac_stream_params *sp, const bnflac_window *d_windows,
+                                               uint32_t nstreams, uint32_t row_samples, uint64_t row_bytes, uint8_t *d_rows,
+                                               uint32_t *d_status, void *hs) {
+    if (!ctx || !sp) return fail("bnflac_gather_ranges: null argument");
+    DevGuard dg(ctx->device); /* the launch on the context's device */
+    if (!d_status || (nstreams && (!d_windows || (row_samples && !d_rows)))) return fail("bnflac_gather_ranges: null output");
+    if (pcm_bytes && !d_pcm) return fail("bnflac_gather_ranges: null d_pcm");
+    if (fmt == BNFLAC_OUT_PLANAR32)
+        return fail("bnflac_gather_ranges: BNFLAC_OUT_PLANAR32 is channel-major per frame, a window of it is no byte range");
+    if (fmt < 0 || fmt > 3) return fail("bnflac_gather_ranges: bad out_format");
+    if (sp->channels < 1 || sp->channels > 8) return fail("bnflac_gather_ranges: channels must be 1..8");
+    if ((((uintptr_t)d_pcm) | ((uintptr_t)d_rows)) & 15u)
+        return fail("bnflac_gather_ranges: d_pcm and d_rows must be 16-byte aligned");
+    if (((uintptr_t)d_windows) & 7u) return fail("bnflac_gather_ranges: d_windows must be 8-byte aligned");
+    if (nstreams >= (1u << 30)) return fail("bnflac_gather_ranges: too many streams");
+    const uint32_t stride = bnflac_out_stride(fmt, sp);
+    if (row_bytes < (uint64_t)row_samples * stride) return fail("bnflac_gather_ranges: row_bytes below row_samples * stride");
+    hipError_t e = bnf_launch_gather_ranges(d_pcm, pcm_bytes, stride, (const bnf_window *)d_windows, nstreams, row_samples,
+                                            row_bytes, d_rows, d_status, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_gather_ranges: ") + hipGetErrorString(e));
 }
 
 /* ====================================================================== */

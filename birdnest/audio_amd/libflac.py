@@ -128,6 +128,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_debug_set_decode_sys", "bnflac_debug_decode_seg_launches", "bnflac_md5_interleaved32", "bnflac_index_stream",
                  "bnflac_index_streams", "bnflac_md5_layout", "bnflac_md5_streams",
                  "bnflac_scan_streams", "bnflac_scan_stream_host",
+                 "bnflac_select_ranges", "bnflac_select_ranges_host", "bnflac_gather_ranges",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -220,6 +221,14 @@ def load() -> ctypes.CDLL:
     L.bnflac_scan_streams.argtypes = [p, p, ctypes.c_uint64, p, ctypes.c_uint32, p, p, p, p, p]
     L.bnflac_scan_stream_host.restype = i
     L.bnflac_scan_stream_host.argtypes = [p, ctypes.c_uint64, p, p]
+    L.bnflac_select_ranges.restype = i
+    L.bnflac_select_ranges.argtypes = [p, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, p, ctypes.c_uint32, p, p, p,
+                                       p, p]
+    L.bnflac_select_ranges_host.restype = i
+    L.bnflac_select_ranges_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, p, p]
+    L.bnflac_gather_ranges.restype = i
+    L.bnflac_gather_ranges.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                       p, p, p]
     _LIB = L
     return L
 
@@ -375,6 +384,68 @@ def scan_stream_host(data):
 def meta_array(raw: np.ndarray) -> np.ndarray:
     """View a uint8 buffer of scan_streams records as a structured array."""
     return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=STREAM_META_DTYPE)
+
+
+class SampleRange(ctypes.Structure):
+    """bnflac_sample_range: one stream's window of select_ranges, in the stream's own samples."""
+    _fields_ = [("first_sample", ctypes.c_uint64), ("nsamples", ctypes.c_uint64)]
+
+
+class Window(ctypes.Structure):
+    """bnflac_window: one stream's record of select_ranges, what gather_ranges reads."""
+    _fields_ = [("pcm_first", ctypes.c_uint64), ("nsamples", ctypes.c_uint64), ("skip", ctypes.c_uint32),
+                ("first_frame", ctypes.c_uint32), ("nframes", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+SAMPLE_RANGE_DTYPE = np.dtype([("first_sample", "<u8"), ("nsamples", "<u8")])
+WINDOW_BYTES = 32
+WINDOW_DTYPE = np.dtype([("pcm_first", "<u8"), ("nsamples", "<u8"), ("skip", "<u4"), ("first_frame", "<u4"),
+                         ("nframes", "<u4"), ("flags", "<u4")])
+assert SAMPLE_RANGE_DTYPE.itemsize == ctypes.sizeof(SampleRange) == 16
+assert WINDOW_DTYPE.itemsize == ctypes.sizeof(Window) == WINDOW_BYTES
+WIN_CLIPPED, WIN_EMPTY = 1, 2          # Window.flags
+SEL_OVERFLOW, SEL_BAD_TABLES = 1, 2    # select_ranges status word 0
+TO_THE_END = (1 << 64) - 1             # SampleRange.nsamples: up to the stream's end
+
+
+def window_array(raw: np.ndarray) -> np.ndarray:
+    """View a uint8 buffer of select_ranges window records as a structured array."""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=WINDOW_DTYPE)
+
+
+def sample_ranges(ranges) -> np.ndarray:
+    """[(first_sample, nsamples)] -> the table of select_ranges (SAMPLE_RANGE_DTYPE)."""
+    table = np.zeros(len(ranges), dtype=SAMPLE_RANGE_DTYPE)
+    for k, (first, n) in enumerate(ranges):
+        if not (0 <= first <= TO_THE_END and 0 <= n <= TO_THE_END):
+            raise ValueError(f"stream {k}: a window is two unsigned 64-bit numbers")
+        table[k] = (first, n)
+    return table
+
+
+def select_ranges_host(info: np.ndarray, cap: int, stream_frames, stream_samples, ranges, sel_cap: int):
+    """select_ranges over host tables (bnflac_select_ranges_host, no GPU).  info: FRAME_INFO_DTYPE
+    records (at least cap of them); ranges: [(first_sample, nsamples)] or a SAMPLE_RANGE_DTYPE array.
+    -> (sel_info[sel_cap], sel_frames uint32[n+1], sel_samples uint64[n+1], windows[n], status uint32[4])"""
+    info = np.ascontiguousarray(info, dtype=FRAME_INFO_DTYPE)
+    sf = np.ascontiguousarray(stream_frames, dtype=np.uint32)
+    ss = np.ascontiguousarray(stream_samples, dtype=np.uint64)
+    n = len(sf) - 1
+    if n < 0 or len(ss) != n + 1 or len(info) < min(cap, int(sf.max(initial=0))):
+        raise ValueError("stream_frames and stream_samples hold nstreams + 1 entries, info the records below cap")
+    r = ranges if isinstance(ranges, np.ndarray) and ranges.dtype == SAMPLE_RANGE_DTYPE else sample_ranges(ranges)
+    r = np.ascontiguousarray(r)
+    if len(r) != n:
+        raise ValueError("one window per stream")
+    sel = np.zeros(sel_cap, dtype=FRAME_INFO_DTYPE)
+    sel_f, sel_s = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint64)
+    win, status = np.zeros(n, dtype=WINDOW_DTYPE), np.zeros(4, np.uint32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    rc = load().bnflac_select_ranges_host(vp(info), cap, vp(sf), vp(ss), n, vp(r), vp(sel), sel_cap, vp(sel_f), vp(sel_s),
+                                          vp(win), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return sel, sel_f, sel_s, win, status
 
 
 def stream_table(streams, nbytes: int) -> np.ndarray:
@@ -617,6 +688,123 @@ class BatchDecoder:
         if rc != 0:
             raise RuntimeError(self.L.bnflac_last_error().decode())
         return d_md5, d_verdict, d_status
+
+    def select_ranges(self, d_offsets, d_info, cap: int, d_stream_frames, d_stream_samples, nstreams: int, ranges,
+                      sel_cap: int, stream=None):
+        """Cut index_streams' tables down to the frames one sample window per stream needs
+        (bnflac_select_ranges).  d_offsets (or None), d_info, cap, d_stream_frames, d_stream_samples:
+        index_streams' outputs and its cap.  ranges: [(first_sample, nsamples)] per stream
+        (TO_THE_END: up to the stream's end), or the same on the device (64-bit, 2 words per stream).
+        -> (d_sel_offsets int64[sel_cap], d_sel_info uint8[sel_cap*128] ready for
+            decode_parsed(nframes=sel_cap), d_sel_frames int32[n+1], d_sel_samples int64[n+1],
+            d_windows uint8[n*32] for gather_ranges, d_status int32[4]),
+        all on the device and not synchronised, like index_streams."""
+        import torch
+        dev = d_info.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        on_device = isinstance(ranges, torch.Tensor)
+        if on_device:
+            if not ranges.is_cuda or ranges.element_size() != 8 or ranges.numel() != 2 * nstreams or not ranges.is_contiguous():
+                raise ValueError("device windows are a contiguous CUDA tensor of 2 64-bit words per stream")
+            d_ranges = ranges
+        else:
+            table = sample_ranges(ranges)
+            if len(table) != nstreams:
+                raise ValueError("one window per stream")
+        with torch.cuda.stream(s):
+            if not on_device:
+                d_ranges = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev) if nstreams else None
+            d_sel_offs = torch.zeros(max(sel_cap, 1), dtype=torch.int64, device=dev)
+            d_sel_info = torch.zeros(max(sel_cap, 1) * FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
+            d_sel_f = torch.zeros(nstreams + 1, dtype=torch.int32, device=dev)
+            d_sel_s = torch.zeros(nstreams + 1, dtype=torch.int64, device=dev)
+            d_win = torch.zeros(max(nstreams, 1) * WINDOW_BYTES, dtype=torch.uint8, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self.L.bnflac_select_ranges(self.ctx, vp(d_offsets), vp(d_info), cap, vp(d_stream_frames),
+                                         vp(d_stream_samples), nstreams, vp(d_ranges) if nstreams else None,
+                                         vp(d_sel_offs) if d_offsets is not None else None, vp(d_sel_info), sel_cap,
+                                         vp(d_sel_f), vp(d_sel_s), vp(d_win), vp(d_status), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_sel_offs, d_sel_info, d_sel_f, d_sel_s, d_win, d_status
+
+    def gather_ranges(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, row_samples: int,
+                      row_bytes: Optional[int] = None, d_rows=None, stream=None, pcm_bytes=None):
+        """The windows of a decoded selection as rows of one shape (bnflac_gather_ranges): row s is
+        min(window s's nsamples, row_samples) sample frames of d_pcm from its pcm_first, then zeros.
+        row_bytes: the distance between rows (default: row_samples * stride); d_rows: the output
+        (default: a new uint8 tensor of nstreams * row_bytes, whose bytes between rows are zero);
+        pcm_bytes: the decoded size (default: all of d_pcm).
+        -> (d_rows, d_status int32[4]), on the device and not synchronised."""
+        import torch
+        dev = d_pcm.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        nbytes = d_pcm.numel() * d_pcm.element_size()
+        width = row_samples * out_stride(fmt, sp)
+        row_bytes = width if row_bytes is None else row_bytes
+        with torch.cuda.stream(s):
+            if d_rows is None:
+                d_rows = torch.zeros(max(nstreams * row_bytes, 1), dtype=torch.uint8, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        if nstreams and d_rows.numel() * d_rows.element_size() < (nstreams - 1) * row_bytes + width:
+            raise ValueError("d_rows is too small for nstreams rows")
+        rc = self.L.bnflac_gather_ranges(self.ctx, ctypes.c_void_p(d_pcm.data_ptr()),
+                                         nbytes if pcm_bytes is None else min(pcm_bytes, nbytes), fmt, ctypes.byref(sp),
+                                         ctypes.c_void_p(d_windows.data_ptr()), nstreams, row_samples, row_bytes,
+                                         ctypes.c_void_p(d_rows.data_ptr()), ctypes.c_void_p(d_status.data_ptr()),
+                                         self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_rows, d_status
+
+    def decode_windows(self, d_bytes, nbytes: int, ranges_bytes, windows, nsamples: int, sp: StreamParams, fmt: int,
+                       cap: Optional[int] = None, cand_cap: int = 0, stream=None):
+        """nsamples sample frames from a position of its own in every .flac file of a buffer:
+        scan_streams -> index_streams -> select_ranges -> decode_parsed(nframes = sel_cap) ->
+        gather_ranges, with no host synchronisation and nothing read back.
+        ranges_bytes: the files, as for scan_streams; sp: the parameters every file must have (others
+        are emptied by the scan and give zero rows); windows: one first sample per stream, or
+        [(first_sample, n)] with n <= nsamples, or a device tensor of 2 64-bit words per stream;
+        cap, cand_cap: as for index_streams (cap defaults to nbytes // 16 + 16).
+        Sizes, for n = nsamples >= 1: sel_cap = nstreams * ((n - 1) // min_blocksize + 2) records (only
+        a stream's last frame may be shorter than min_blocksize) and a compact PCM of
+        nstreams * (n + 2 * (max_blocksize - 1)) sample frames.  A stream whose STREAMINFO understates
+        its frames shows up as bit 0 of the select status (and its row may be zero), not as a fault.
+        -> (rows, status): rows int32[nstreams, nsamples, channels] for OUT_INTERLEAVED32, else
+        uint8[nstreams, nsamples * stride]; status: the device status words of each stage,
+        {"scan", "index", "select", "gather"} -> int32[4]."""
+        import torch
+        if nsamples < 1:
+            raise ValueError("nsamples must be at least 1")
+        if fmt == OUT_PLANAR32:
+            raise ValueError("OUT_PLANAR32 is channel-major per frame: a window of it is no byte range")
+        if sp.min_blocksize < 1 or sp.max_blocksize < sp.min_blocksize:
+            raise ValueError("sp must carry STREAMINFO's min_blocksize and max_blocksize")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        dev = d_bytes.device
+        n = ranges_bytes.numel() // 4 if isinstance(ranges_bytes, torch.Tensor) else len(ranges_bytes)
+        if not isinstance(windows, torch.Tensor):
+            windows = [(w, nsamples) if np.isscalar(w) else tuple(w) for w in windows]
+        cap = nbytes // 16 + 16 if cap is None else cap
+        sel_cap = n * ((nsamples - 1) // sp.min_blocksize + 2)
+        stride = out_stride(fmt, sp)
+        d_tab, _, _, st_scan = self.scan_streams(d_bytes, nbytes, ranges_bytes, expect=sp, stream=s)
+        d_offs, _, d_info, d_sf, d_ss, st_index = self.index_streams(d_bytes, nbytes, d_tab, sp, cap, cand_cap=cand_cap,
+                                                                     stream=s)
+        _, d_sel_info, _, _, d_win, st_select = self.select_ranges(d_offs, d_info, cap, d_sf, d_ss, n, windows, sel_cap,
+                                                                   stream=s)
+        with torch.cuda.stream(s):
+            pcm_bytes = n * (nsamples + 2 * (sp.max_blocksize - 1)) * stride
+            d_pcm = torch.zeros(max((pcm_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=dev)
+        self.decode_parsed(d_bytes, nbytes, sel_cap, sp, fmt, d_pcm, d_sel_info, stream=s)
+        d_rows, st_gather = self.gather_ranges(d_pcm, fmt, sp, d_win, n, nsamples, stream=s)
+        with torch.cuda.stream(s):
+            if fmt == OUT_INTERLEAVED32:
+                rows = d_rows[: n * nsamples * stride].view(torch.int32).view(n, nsamples, sp.channels)
+            else:
+                rows = d_rows[: n * nsamples * stride].view(n, nsamples * stride)
+        return rows, {"scan": st_scan, "index": st_index, "select": st_select, "gather": st_gather}
 
     def crc_handoff(self, nframes: int) -> np.ndarray:
         """Debug: the CRC-16 hand-off of the last parse_frames call, [nframes, 8] uint32."""

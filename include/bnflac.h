@@ -14,7 +14,8 @@
  * buffer go through it without the host reading anything back: bnflac_scan_streams (metadata)
  * -> bnflac_index_streams (frames) -> bnflac_parse_frames / bnflac_decode_parsed (PCM) ->
  * bnflac_md5_streams (verification), each asynchronous on the caller's HIP stream and chained by
- * device tables.
+ * device tables.  For one sample window per stream instead of whole streams, bnflac_select_ranges
+ * goes between index and decode and bnflac_gather_ranges after the decode.
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -359,6 +360,88 @@ BNFLAC_API int bnflac_md5_streams(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_
                                   const bnflac_stream_params *sp, const uint64_t *d_stream_samples,
                                   uint32_t nstreams, const uint8_t *d_expected, uint8_t *d_md5,
                                   uint32_t *d_verdict, uint32_t *d_status, void *hip_stream);
+
+/* One stream's window of bnflac_select_ranges, in the stream's own samples. */
+typedef struct {
+    uint64_t first_sample, nsamples;
+} bnflac_sample_range;
+
+/* Per-stream result record of bnflac_select_ranges (32 bytes), device-resident. */
+typedef struct {
+    uint64_t pcm_first;     /* sample frame of the compact PCM at which the window starts (= d_sel_samples[s] + skip) */
+    uint64_t nsamples;      /* samples of the window after clipping at the stream's end */
+    uint32_t skip;          /* samples of the first selected frame in front of the window (< its blocksize) */
+    uint32_t first_frame;   /* position in the index's tables of the first selected frame (d_stream_frames[s] when none) */
+    uint32_t nframes;       /* frames selected */
+    uint32_t flags;         /* bit 0 clipped by the stream's end, bit 1 empty */
+} bnflac_window;
+
+/* Cut the tables of bnflac_index_streams down to the frames that one sample window per stream
+ * needs, on the device: index -> bnflac_select_ranges -> bnflac_decode_parsed(nframes = sel_cap)
+ * -> bnflac_gather_ranges decodes "samples [a, a + n) of every stream" without decoding the rest
+ * and without the host reading anything back.  d_frame_offsets (may be NULL with d_sel_offsets),
+ * d_info, cap, d_stream_frames and d_stream_samples are the index call's outputs and its cap;
+ * d_info and d_sel_info are 16-byte aligned.
+ * Per stream s, with T = d_stream_samples[s + 1] - d_stream_samples[s], and for every frame i of
+ * [d_stream_frames[s], d_stream_frames[s + 1]) its local start L_i = d_info[i].out_sample -
+ * d_stream_samples[s] and its blocksize b_i:
+ *   lo = min(first_sample, T), hi = min(lo + nsamples, T), the sum saturating (nsamples =
+ *   UINT64_MAX: to the end).  hi == lo: the window is empty (flags bit 1, nframes 0, skip 0,
+ *   nsamples 0, pcm_first = d_sel_samples[s]).  Else the frames with L_i < hi and L_i + b_i > lo
+ *   are selected, a contiguous run [a, b) (a frame that only touches the window, L_i == hi or
+ *   L_i + b_i == lo, is not): first_frame = a, nframes = b - a, skip = lo - L_a, nsamples =
+ *   hi - lo.  flags bit 0 when first_sample + nsamples (saturating) exceeds T.
+ * The selected records are copied byte for byte apart from out_sample, which becomes
+ * d_sel_samples[s] + (L_i - L_a): the selection decodes into a compact PCM in which stream s owns
+ * the sample frames [d_sel_samples[s], d_sel_samples[s + 1]), the frame-aligned hull of its
+ * window.  d_sel_offsets (may be NULL) gets the matching d_frame_offsets entries.  d_sel_frames
+ * and d_sel_samples (nstreams + 1 entries each) are the exclusive prefixes of the frames and
+ * samples selected per stream; their last entry is the true total.  Positions [total, sel_cap) of
+ * d_sel_info are filler records: zeros apart from status 3 (skipped) and err -1, d_sel_offsets 0;
+ * every decode kernel leaves a record alone whose status is not OK, so bnflac_decode_parsed can
+ * run over sel_cap records without the count being read back.
+ * d_status (device, 4 words): [0] bit 0 more frames selected than sel_cap (the records below
+ * sel_cap are written, the tables are the true prefixes, a stream whose frames all lie below
+ * sel_cap is complete), bit 1 the tables are unusable (d_stream_frames[nstreams] > cap: the index
+ * overflowed, or d_stream_frames / d_stream_samples descend): nothing is selected, both prefix
+ * tables are zero, every window is empty and every record below sel_cap is filler; [1] frames
+ * selected; [2] streams with a non-empty window; [3] streams clipped.  nstreams == 0 writes a
+ * zero status and fills d_sel_info.  A failed index call (d_stream_frames all zero) selects nothing.
+ * Nothing at or past position cap of the index's tables is read, nothing at or past sel_cap is
+ * written, and no loop is bounded by a table's contents: over out_sample values the index did not
+ * write, the searches still end inside the stream's frames, with some window.  Asynchronous on
+ * hip_stream, no host synchronisation; the only allocation is a scratch kept in ctx that grows
+ * with nstreams. */
+BNFLAC_API int bnflac_select_ranges(bnflac_ctx *ctx, const uint64_t *d_frame_offsets, const bnflac_frame_info *d_info,
+                                    uint32_t cap, const uint32_t *d_stream_frames, const uint64_t *d_stream_samples,
+                                    uint32_t nstreams, const bnflac_sample_range *d_ranges, uint64_t *d_sel_offsets,
+                                    bnflac_frame_info *d_sel_info, uint32_t sel_cap, uint32_t *d_sel_frames,
+                                    uint64_t *d_sel_samples, bnflac_window *d_windows, uint32_t *d_status,
+                                    void *hip_stream);
+
+/* The same selection over tables in host memory, with the same results; no GPU needed.  0, or -1
+ * for a null argument. */
+BNFLAC_API int bnflac_select_ranges_host(const bnflac_frame_info *info, uint32_t cap, const uint32_t *stream_frames,
+                                         const uint64_t *stream_samples, uint32_t nstreams,
+                                         const bnflac_sample_range *ranges, bnflac_frame_info *sel_info, uint32_t sel_cap,
+                                         uint32_t *sel_frames, uint64_t *sel_samples, bnflac_window *windows,
+                                         uint32_t status[4]);
+
+/* The windows of a decoded selection as rows of one shape.  With stride = bnflac_out_stride(
+ * out_format, sp), row s starts at d_rows + s * row_bytes: its first min(d_windows[s].nsamples,
+ * row_samples) * stride bytes are the bytes of d_pcm from d_windows[s].pcm_first * stride, the rest
+ * up to row_samples * stride is zero, and the bytes from there to row_bytes are not written.
+ * d_pcm and d_rows are 16-byte aligned, d_pcm's allocation at least round_up(pcm_bytes, 16) bytes;
+ * row_bytes is arbitrary but not below row_samples * stride (a negative return), and
+ * BNFLAC_OUT_PLANAR32 (channel-major per frame) is refused (a negative return).  Any window table
+ * will do, not only one bnflac_select_ranges wrote: a non-empty window that does not lie inside
+ * pcm_bytes gives a zero row.  d_status (device, 4 words): [0] bit 0 some such window, [1] how
+ * many, [2] rows cut at row_samples, [3] 0.  Nothing outside [0, round_up(pcm_bytes, 16)) is read.
+ * Asynchronous on hip_stream, no host synchronisation, no allocation. */
+BNFLAC_API int bnflac_gather_ranges(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int out_format,
+                                    const bnflac_stream_params *sp, const bnflac_window *d_windows, uint32_t nstreams,
+                                    uint32_t row_samples, uint64_t row_bytes, uint8_t *d_rows, uint32_t *d_status,
+                                    void *hip_stream);
 
 /* ======================== Part 3: streaming reader ======================= */
 
