@@ -3421,136 +3421,143 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
         nst = 0;
     };
     const uint64_t t_loop = tnow(tmon);
-    for (uint32_t kc = 0; kc < nchunks; kc++) {
-        const uint64_t ta = tnow(tmon);
-        const uint32_t n0 = kc * ST2_CHK;
-        const bool valid = ok && n0 < bs;
-        bool fast = valid && n0 >= 8u && n0 + ST2_CHK <= bs && !(ablate & (BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE));
-        if (fast) { /* partition headers at the chunk boundary (aligned partitions) */
-            if (z0.left == 0 && z0.parts_left()) st_partition(z0, bs);
-            if (z1.left == 0 && z1.parts_left()) st_partition(z1, bs);
-            fast = !z0.esc() && !z1.esc() && z0.left >= ST2_CHK && z1.left >= ST2_CHK;
-        }
-        const bool fused = !any_lane(valid && !fast);
-        u32x4 pk[4], pk0[4]; /* STG: the chunk's eight 16-byte units of this lane's frame run (128 bytes): pk0 from the first half, pk from the second */
-        if (fused) {
-            if (valid) {
-                STAT(z0.b.stats, 0);
-                int32_t pre0, pre1;
-                st_pre2<7>(z0, z1, pre0, pre1); /* older taps of the chunk's first sample */
-                st_resync(z0.b, lane);
-                st_resync(z1.b, lane);
-                /* the chunk's 4 groups of 8 samples, a refill after the second; AS >= 0: the
-                 * wave's one assignment, no wasted bits (st_decor4t), compiled per assignment */
-                auto chunk = [&](auto as_c) {
-                    constexpr int AS = decltype(as_c)::value;
-                    auto group = [&](auto g_c, uint32_t nb) {
-                        constexpr uint32_t G = decltype(g_c)::value;
-                        int32_t L[4], R[4];
-                        const uint32_t nq = nst + (STG ? 0u : G * 2u * ST_SPG); /* stores issued since the DMAs (at least) */
+    /* The chunk loop, one instance per as_fix (AS): the assignment is a property of the whole
+     * loop, so each instance keeps the loop-carried state (both channels, pk / pk0, the fold)
+     * in registers of its own from chunk to chunk.  A dispatch inside the chunk made the five
+     * fused bodies meet at every chunk, and the register allocator reconciled them with
+     * blocks of ~50 v_mov_b32 on the way in and out. */
+    auto chunks = [&](auto as_c) __attribute__((always_inline)) {
+        constexpr int AS = decltype(as_c)::value;
+        for (uint32_t kc = 0; kc < nchunks; kc++) {
+            const uint64_t ta = tnow(tmon);
+            const uint32_t n0 = kc * ST2_CHK;
+            const bool valid = ok && n0 < bs;
+            bool fast = valid && n0 >= 8u && n0 + ST2_CHK <= bs && !(ablate & (BNF_ABLATE_NO_RESTORE | BNF_ABLATE_NO_RICE));
+            if (fast) { /* partition headers at the chunk boundary (aligned partitions) */
+                if (z0.left == 0 && z0.parts_left()) st_partition(z0, bs);
+                if (z1.left == 0 && z1.parts_left()) st_partition(z1, bs);
+                fast = !z0.esc() && !z1.esc() && z0.left >= ST2_CHK && z1.left >= ST2_CHK;
+            }
+            const bool fused = !any_lane(valid && !fast);
+            u32x4 pk[4], pk0[4]; /* STG: the chunk's eight 16-byte units of this lane's frame run (128 bytes): pk0 from the first half, pk from the second */
+            if (fused) {
+                if (valid) {
+                    STAT(z0.b.stats, 0);
+                    int32_t pre0, pre1;
+                    st_pre2<7>(z0, z1, pre0, pre1); /* older taps of the chunk's first sample */
+                    st_resync(z0.b, lane);
+                    st_resync(z1.b, lane);
+                    /* the chunk's 4 groups of 8 samples, a refill after the second; AS >= 0: the
+                     * wave's one assignment, no wasted bits (st_decor4t), the loop instance's */
+                    {
+                        auto group = [&](auto g_c, uint32_t nb) {
+                            constexpr uint32_t G = decltype(g_c)::value;
+                            int32_t L[4], R[4];
+                            const uint32_t nq = nst + (STG ? 0u : G * 2u * ST_SPG); /* stores issued since the DMAs (at least) */
 #define FPAIR(T) st_fused_pair<T, FMT, AS, 2 * G, 4>(z0, z1, L, R, limit, trunc, nq, as_uni, as_u, as, dst, nb, al, bs, sto, pk, pre0, pre1, lane, anyw)
-                        FPAIR(0); FPAIR(2); FPAIR(4); FPAIR(6);
+                            FPAIR(0); FPAIR(2); FPAIR(4); FPAIR(6);
 #undef FPAIR
-                    };
+                        };
 #pragma unroll 1
-                    for (uint32_t h = 0; h < 2; h++) { /* two halves of 16 samples, a refill between */
-                        const uint32_t nb = n0 + 16u * h;
-                        group(std::integral_constant<uint32_t, 0>(), nb);
-                        group(std::integral_constant<uint32_t, 1>(), nb + 8u);
-                        if (h == 0) {
-                            if (STG) {
+                        for (uint32_t h = 0; h < 2; h++) { /* two halves of 16 samples, a refill between */
+                            const uint32_t nb = n0 + 16u * h;
+                            group(std::integral_constant<uint32_t, 0>(), nb);
+                            group(std::integral_constant<uint32_t, 1>(), nb + 8u);
+                            if (h == 0) {
+                                if (STG) {
 #pragma unroll
-                                for (int u = 0; u < 4; u++) pk0[u] = pk[u];
-                            } else if (sto) {
-                                nst += 4u * ST_SPG;
+                                    for (int u = 0; u < 4; u++) pk0[u] = pk[u];
+                                } else if (sto) {
+                                    nst += 4u * ST_SPG;
+                                }
+                                refill(true); /* the chunk's first half is decoded: n0 + 16 < bs */
+                                st_resync(z0.b, lane);
+                                st_resync(z1.b, lane);
                             }
-                            refill(true); /* the chunk's first half is decoded: n0 + 16 < bs */
-                            st_resync(z0.b, lane);
-                            st_resync(z1.b, lane);
                         }
                     }
-                };
-                switch (as_fix) {
-                case 0: chunk(std::integral_constant<int, 0>()); break;
-                case 1: chunk(std::integral_constant<int, 1>()); break;
-                case 2: chunk(std::integral_constant<int, 2>()); break;
-                case 3: chunk(std::integral_constant<int, 3>()); break;
-                default: chunk(std::integral_constant<int, -1>()); break;
+                    z0.left -= ST2_CHK;
+                    z1.left -= ST2_CHK;
+                } else {
+                    refill(false); /* the wave's mid-chunk refill, for this lane's wait */
                 }
-                z0.left -= ST2_CHK;
-                z1.left -= ST2_CHK;
+                if (!STG && sto && any_lane(valid)) nst += 4u * ST_SPG;
             } else {
-                refill(false); /* the wave's mid-chunk refill, for this lane's wait */
-            }
-            if (!STG && sto && any_lane(valid)) nst += 4u * ST_SPG;
-        } else {
-            STAT(z0.b.stats, 1);
+                STAT(z0.b.stats, 1);
 #pragma unroll 1
-            for (uint32_t g = 0; g < ST2_CHK / 8; g++) {
-                int32_t L[4], R[4];
-                const uint32_t nb = n0 + g * 8u;
-                bool st0, st1;
+                for (uint32_t g = 0; g < ST2_CHK / 8; g++) {
+                    int32_t L[4], R[4];
+                    const uint32_t nb = n0 + g * 8u;
+                    bool st0, st1;
 #define GSTEP(T) st_gen_step<T, FMT>(z0, z1, L, R, limit, trunc, nst, as_uni, as_u, as, dst, nb + T, valid, al, bs, sto)
-                GSTEP(0); GSTEP(1); GSTEP(2);
-                st0 = GSTEP(3);
-                if (any_lane(st0)) nst += 1u; /* at least one store instruction */
-                GSTEP(4); GSTEP(5); GSTEP(6);
-                st1 = GSTEP(7);
-                if (any_lane(st1)) nst += 1u;
+                    GSTEP(0); GSTEP(1); GSTEP(2);
+                    st0 = GSTEP(3);
+                    if (any_lane(st0)) nst += 1u; /* at least one store instruction */
+                    GSTEP(4); GSTEP(5); GSTEP(6);
+                    st1 = GSTEP(7);
+                    if (any_lane(st1)) nst += 1u;
 #undef GSTEP
-                if (g == 1) refill(valid && nb + 8u < bs);
-            }
-        }
-        const uint64_t tb = tnow(tmon);
-        tm_dec += tb - ta;
-        /* the fold may take the cursor's own line when channel 1 has more than that line's
-         * bits (and the two-word lookahead's) still to come: the rest of the partition at k + 1
-         * bits a sample or more, every later sample at one or more */
-        const uint32_t rest = bs - min(bs, n0 + ST2_CHK), inp = z1.esc() ? 0u : min(rest, z1.left);
-        refill(valid && n0 + ST2_CHK < bs, true, inp * z1.k1 + (rest - inp) >= 576u);
-        const uint64_t tc = tnow(tmon);
-        tm_ref += tc - tb;
-        if (STG && fused) {
-            /* flush: every frame's 128-byte run of the chunk as one whole cache line.  Two
-             * rounds of 32 frames through the 4 KB staging tile: the round's lanes write their
-             * eight units (the slot of unit u of frame f is u ^ (f & 7): conflict-free
-             * ds_write_b128), then lane l reads unit l & 7 of frame (l >> 3) + 8 i and stores
-             * it: each store instruction writes 8 whole lines.  Every lane is active here
-             * (a lane whose frame has ended stores nothing: its run address is 0). */
-            uint64_t run = (valid && sto) ? (uint64_t)(uintptr_t)(dst + (uint64_t)n0 * 4u) : 0ull;
-            /* timing ablation 0x10000000: the same stores into one 64 KB window per XCD (an
-             * L2-resident footprint: the HBM write traffic without the instructions); wrong PCM */
-            if ((ablate & BNF_ABLATE_HOT_WINDOW) && run && out_bytes >= (1u << 20)) /* the window needs 513 KB */
-                run = (uint64_t)(uintptr_t)(out + (uint64_t)(blockIdx.x & 7u) * 65536u + lane * 1024u + ((n0 * 4u) & 1023u));
-            const uint32_t rlo = (uint32_t)run, rhi = (uint32_t)(run >> 32);
-            const uint32_t fr = lane & 31u, ul = lane & 7u;
-#pragma unroll
-            for (uint32_t r = 0; r < 2; r++) {
-                if ((lane >> 5) == r) {
-#pragma unroll
-                    for (uint32_t u = 0; u < 8; u++) lds_st128(stg + fr * 8u + (u ^ (fr & 7u)), u < 4 ? pk0[u] : pk[u - 4]);
-                }
-                lds_sync();
-                /* the round's four units and run addresses, one wait for all of them */
-                u32x4 v[4];
-                uint64_t a[4];
-#pragma unroll
-                for (uint32_t i = 0; i < 4; i++) {
-                    const uint32_t f = (lane >> 3) + 8u * i;      /* frame within the round */
-                    v[i] = lds_ld128(stg + f * 8u + (ul ^ (f & 7u)));
-                    const uint32_t src = (32u * r + f) * 4u;     /* its lane, for ds_bpermute */
-                    a[i] = ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)rhi) << 32) |
-                           (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)rlo);
-                }
-                lds_sync();
-#pragma unroll
-                for (uint32_t i = 0; i < 4; i++) {
-                    if (a[i]) gst128(a[i] + 16u * ul, v[i]);
-                    if (any_lane(a[i] != 0)) nst += 1u;
+                    if (g == 1) refill(valid && nb + 8u < bs);
                 }
             }
+            const uint64_t tb = tnow(tmon);
+            tm_dec += tb - ta;
+            /* the fold may take the cursor's own line when channel 1 has more than that line's
+             * bits (and the two-word lookahead's) still to come: the rest of the partition at k + 1
+             * bits a sample or more, every later sample at one or more */
+            const uint32_t rest = bs - min(bs, n0 + ST2_CHK), inp = z1.esc() ? 0u : min(rest, z1.left);
+            refill(valid && n0 + ST2_CHK < bs, true, inp * z1.k1 + (rest - inp) >= 576u);
+            const uint64_t tc = tnow(tmon);
+            tm_ref += tc - tb;
+            if (STG && fused) {
+                /* flush: every frame's 128-byte run of the chunk as one whole cache line.  Two
+                 * rounds of 32 frames through the 4 KB staging tile: the round's lanes write their
+                 * eight units (the slot of unit u of frame f is u ^ (f & 7): conflict-free
+                 * ds_write_b128), then lane l reads unit l & 7 of frame (l >> 3) + 8 i and stores
+                 * it: each store instruction writes 8 whole lines.  Every lane is active here
+                 * (a lane whose frame has ended stores nothing: its run address is 0). */
+                uint64_t run = (valid && sto) ? (uint64_t)(uintptr_t)(dst + (uint64_t)n0 * 4u) : 0ull;
+                /* timing ablation 0x10000000: the same stores into one 64 KB window per XCD (an
+                 * L2-resident footprint: the HBM write traffic without the instructions); wrong PCM */
+                if ((ablate & BNF_ABLATE_HOT_WINDOW) && run && out_bytes >= (1u << 20)) /* the window needs 513 KB */
+                    run = (uint64_t)(uintptr_t)(out + (uint64_t)(blockIdx.x & 7u) * 65536u + lane * 1024u + ((n0 * 4u) & 1023u));
+                const uint32_t rlo = (uint32_t)run, rhi = (uint32_t)(run >> 32);
+                const uint32_t fr = lane & 31u, ul = lane & 7u;
+#pragma unroll
+                for (uint32_t r = 0; r < 2; r++) {
+                    if ((lane >> 5) == r) {
+#pragma unroll
+                        for (uint32_t u = 0; u < 8; u++) lds_st128(stg + fr * 8u + (u ^ (fr & 7u)), u < 4 ? pk0[u] : pk[u - 4]);
+                    }
+                    lds_sync();
+                    /* the round's four units and run addresses, one wait for all of them */
+                    u32x4 v[4];
+                    uint64_t a[4];
+#pragma unroll
+                    for (uint32_t i = 0; i < 4; i++) {
+                        const uint32_t f = (lane >> 3) + 8u * i;      /* frame within the round */
+                        v[i] = lds_ld128(stg + f * 8u + (ul ^ (f & 7u)));
+                        const uint32_t src = (32u * r + f) * 4u;     /* its lane, for ds_bpermute */
+                        a[i] = ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)rhi) << 32) |
+                               (uint32_t)__builtin_amdgcn_ds_bpermute((int)src, (int)rlo);
+                    }
+                    lds_sync();
+#pragma unroll
+                    for (uint32_t i = 0; i < 4; i++) {
+                        if (a[i]) gst128(a[i] + 16u * ul, v[i]);
+                        if (any_lane(a[i] != 0)) nst += 1u;
+                    }
+                }
+            }
+            tm_pack += tnow(tmon) - tc;
         }
-        tm_pack += tnow(tmon) - tc;
+    };
+    switch (as_fix) {
+    case 0: chunks(std::integral_constant<int, 0>()); break;
+    case 1: chunks(std::integral_constant<int, 1>()); break;
+    case 2: chunks(std::integral_constant<int, 2>()); break;
+    case 3: chunks(std::integral_constant<int, 3>()); break;
+    default: chunks(std::integral_constant<int, -1>()); break;
     }
     const uint64_t t_loopend = tnow(tmon);
 
