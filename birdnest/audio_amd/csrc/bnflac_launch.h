@@ -235,6 +235,17 @@ hipError_t bnf_launch_select_ranges(const uint64_t *offsets, const bnf_frame_inf
 hipError_t bnf_launch_gather_ranges(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, const bnf_window *windows,
                                     uint32_t nstreams, uint32_t row_samples, uint64_t row_bytes, uint8_t *rows,
                                     uint32_t *status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_f32.hip (no tables, no g_stats, no ablate word)
+ * k_gather_f32: the rule of bnf_pcm_f32.h.  Plane c of stream s = out + (s * planes + c) *
+ * plane_pitch floats (planes = 1 with BNF_F32_MONO in flags, else channels) gets
+ * min(windows[s].nsamples, row_samples) normalised samples from pcm + windows[s].pcm_first * stride
+ * (channel c at c * unit, unit = stride / channels in 2..4), then +0.0f up to row_samples.  pcm and
+ * out 16-byte aligned, pcm's allocation at least round_up(pcm_bytes, 16) bytes.  Zeroes status
+ * (4 words) on s, then launches. */
+hipError_t bnf_launch_gather_f32(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, uint32_t unit, uint32_t bps,
+                                 uint32_t channels, uint32_t flags, const bnf_window *windows, uint32_t nstreams,
+                                 uint32_t row_samples, uint64_t plane_pitch, float *out, uint32_t *status, hipStream_t s);
 } /* extern "C" */
 
 #endif

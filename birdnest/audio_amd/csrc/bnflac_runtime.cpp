@@ -25,6 +25,7 @@
 
 #include "../../../include/bnflac.h"
 #include "bnf_metadata.h"
+#include "bnf_pcm_f32.h"
 #include "bnflac_device.h"
 #include "bnflac_launch.h"
 #include "bnflac_md5.h"
@@ -599,6 +600,57 @@ extern "C" BNFLAC_API int bnflac_gather_ranges(bnflac_ctx *ctx, const uint8_t *d
     hipError_t e = bnf_launch_gather_ranges(d_pcm, pcm_bytes, stride, (const bnf_window *)d_windows, nstreams, row_samples,
                                             row_bytes, d_rows, d_status, (hipStream_t)hs);
     return e == hipSuccess ? 0 : fail(std::string("bnflac_gather_ranges: ") + hipGetErrorString(e));
+}
+
+/* What both bnflac_gather_ranges_f32 calls refuse apart from pointers; fills stride and unit. */
+static const char *gather_f32_refusal(int fmt, const bnflac_stream_params *sp, uint32_t nstreams, uint32_t row_samples,
+                                      uint64_t plane_pitch, uint32_t flags, uint32_t &stride, uint32_t &unit) {
+    if (fmt == BNFLAC_OUT_PLANAR32) return "BNFLAC_OUT_PLANAR32 is channel-major per frame, a window of it is no byte range";
+    if (fmt < 0 || fmt > 3) return "bad out_format";
+    if (sp->channels < 1 || sp->channels > 8) return "channels must be 1..8";
+    if (!bnflac_md5_layout(fmt, sp)) return "the layout's bytes are not the samples (bnflac_md5_layout is 0)";
+    if (flags & ~(uint32_t)BNFLAC_F32_MONO) return "unknown flags";
+    if (plane_pitch < row_samples) return "plane_pitch below row_samples";
+    if (nstreams >= (1u << 30)) return "too many streams";
+    stride = bnflac_out_stride(fmt, sp);
+    unit = stride / sp->channels;
+    return nullptr;
+}
+
+extern "C" BNFLAC_API int bnflac_gather_ranges_f32(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
+                                                   const bnflac_stream_params *sp, const bnflac_window *d_windows,
+                                                   uint32_t nstreams, uint32_t row_samples, uint64_t plane_pitch,
+                                                   uint32_t flags, float *d_out, uint32_t *d_status, void *hs) {
+    if (!ctx || !sp) return fail("bnflac_gather_ranges_f32: null argument");
+    DevGuard dg(ctx->device); /* the launch on the context's device */
+    if (!d_status || (nstreams && (!d_windows || (row_samples && !d_out)))) return fail("bnflac_gather_ranges_f32: null output");
+    if (pcm_bytes && !d_pcm) return fail("bnflac_gather_ranges_f32: null d_pcm");
+    uint32_t stride = 0, unit = 0;
+    if (const char *why = gather_f32_refusal(fmt, sp, nstreams, row_samples, plane_pitch, flags, stride, unit))
+        return fail(std::string("bnflac_gather_ranges_f32: ") + why);
+    if ((((uintptr_t)d_pcm) | ((uintptr_t)d_out)) & 15u)
+        return fail("bnflac_gather_ranges_f32: d_pcm and d_out must be 16-byte aligned");
+    if (((uintptr_t)d_windows) & 7u) return fail("bnflac_gather_ranges_f32: d_windows must be 8-byte aligned");
+    hipError_t e = bnf_launch_gather_f32(d_pcm, pcm_bytes, stride, unit, sp->bps, sp->channels, flags,
+                                         (const bnf_window *)d_windows, nstreams, row_samples, plane_pitch, d_out, d_status,
+                                         (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_gather_ranges_f32: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_gather_ranges_f32_host(const uint8_t *pcm, uint64_t pcm_bytes, int fmt,
+                                                        const bnflac_stream_params *sp, const bnflac_window *windows,
+                                                        uint32_t nstreams, uint32_t row_samples, uint64_t plane_pitch,
+                                                        uint32_t flags, float *out, uint32_t status[4]) {
+    if (!sp) return fail("bnflac_gather_ranges_f32_host: null argument");
+    if (!status || (nstreams && (!windows || (row_samples && !out)))) return fail("bnflac_gather_ranges_f32_host: null output");
+    if (pcm_bytes && !pcm) return fail("bnflac_gather_ranges_f32_host: null pcm");
+    uint32_t stride = 0, unit = 0;
+    if (const char *why = gather_f32_refusal(fmt, sp, nstreams, row_samples, plane_pitch, flags, stride, unit))
+        return fail(std::string("bnflac_gather_ranges_f32_host: ") + why);
+    if (bnf_gather_f32_host(pcm, pcm_bytes, stride, unit, sp->bps, sp->channels, flags, (const bnf_window *)windows, nstreams,
+                            row_samples, plane_pitch, out, status) != 0)
+        return fail("bnflac_gather_ranges_f32_host: out of memory");
+    return 0;
 }
 
 /* ====================================================================== */

@@ -129,6 +129,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_index_streams", "bnflac_md5_layout", "bnflac_md5_streams",
                  "bnflac_scan_streams", "bnflac_scan_stream_host",
                  "bnflac_select_ranges", "bnflac_select_ranges_host", "bnflac_gather_ranges",
+                 "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -229,6 +230,12 @@ def load() -> ctypes.CDLL:
     L.bnflac_gather_ranges.restype = i
     L.bnflac_gather_ranges.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                        p, p, p]
+    L.bnflac_gather_ranges_f32.restype = i
+    L.bnflac_gather_ranges_f32.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32,
+                                           ctypes.c_uint64, ctypes.c_uint32, p, p, p]
+    L.bnflac_gather_ranges_f32_host.restype = i
+    L.bnflac_gather_ranges_f32_host.argtypes = [p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.c_uint32, p, p]
     _LIB = L
     return L
 
@@ -487,6 +494,42 @@ def md5_interleaved32(pcm: np.ndarray, channels: int, bps: int) -> bytes:
 def md5_layout(fmt: int, sp: StreamParams) -> int:
     """Bytes per sample of the MD5 message when md5_streams can hash fmt's bytes for sp, else 0."""
     return int(load().bnflac_md5_layout(fmt, ctypes.byref(sp)))
+
+
+F32_MONO = 1  # gather_ranges_f32 flags: one plane per stream, the mean of the channels
+
+
+def f32_layout(sp: StreamParams) -> int:
+    """The narrowest layout gather_ranges_f32 accepts for sp: what decode_windows_f32 decodes into."""
+    if sp.bps == 16 and sp.channels <= 2:
+        return OUT_FLACDECODER
+    return OUT_FILEREADER if sp.bps in (16, 24) else OUT_INTERLEAVED32
+
+
+def gather_ranges_f32_host(pcm: np.ndarray, fmt: int, sp: StreamParams, windows: np.ndarray, row_samples: int,
+                           mono: bool = False, plane_pitch: Optional[int] = None, pcm_bytes: Optional[int] = None):
+    """gather_ranges_f32 over host memory (bnflac_gather_ranges_f32_host, no GPU).  pcm: the decoded
+    bytes (uint8; read as round_up(pcm_bytes, 16) bytes, so shorter arrays are padded with zeros);
+    windows: a WINDOW_DTYPE array.
+    -> (float32[nstreams, planes, row_samples], status uint32[4])"""
+    pcm = np.ascontiguousarray(pcm).view(np.uint8).reshape(-1)
+    nbytes = pcm.size if pcm_bytes is None else min(pcm_bytes, pcm.size)
+    buf = np.zeros((nbytes + 15) // 16 * 16, np.uint8)
+    buf[:nbytes] = pcm[:nbytes]
+    win = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+    n = len(win)
+    planes = 1 if mono else sp.channels
+    pitch = row_samples if plane_pitch is None else plane_pitch
+    if pitch < row_samples:
+        raise ValueError("plane_pitch is below row_samples")
+    out = np.zeros(max(n * planes * pitch, 1), np.float32)
+    status = np.zeros(4, np.uint32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    rc = load().bnflac_gather_ranges_f32_host(vp(buf), nbytes, fmt, ctypes.byref(sp), vp(win), n, row_samples, pitch,
+                                              F32_MONO if mono else 0, vp(out), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return out[: n * planes * pitch].reshape(n, planes, pitch)[:, :, :row_samples], status
 
 
 def streaminfo_md5(data) -> bytes:
@@ -775,13 +818,29 @@ class BatchDecoder:
         uint8[nstreams, nsamples * stride]; status: the device status words of each stage,
         {"scan", "index", "select", "gather"} -> int32[4]."""
         import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        d_pcm, d_win, n, status = self._decode_selection(d_bytes, nbytes, ranges_bytes, windows, nsamples, sp, fmt, cap,
+                                                         cand_cap, s)
+        stride = out_stride(fmt, sp)
+        d_rows, status["gather"] = self.gather_ranges(d_pcm, fmt, sp, d_win, n, nsamples, stream=s)
+        with torch.cuda.stream(s):
+            if fmt == OUT_INTERLEAVED32:
+                rows = d_rows[: n * nsamples * stride].view(torch.int32).view(n, nsamples, sp.channels)
+            else:
+                rows = d_rows[: n * nsamples * stride].view(n, nsamples * stride)
+        return rows, status
+
+    def _decode_selection(self, d_bytes, nbytes, ranges_bytes, windows, nsamples, sp, fmt, cap, cand_cap, s):
+        """The front of decode_windows and decode_windows_f32: scan_streams -> index_streams ->
+        select_ranges -> decode_parsed(nframes = sel_cap) into a compact PCM in fmt, on stream s.
+        -> (d_pcm, d_windows, nstreams, {"scan", "index", "select"} -> int32[4])"""
+        import torch
         if nsamples < 1:
             raise ValueError("nsamples must be at least 1")
         if fmt == OUT_PLANAR32:
             raise ValueError("OUT_PLANAR32 is channel-major per frame: a window of it is no byte range")
         if sp.min_blocksize < 1 or sp.max_blocksize < sp.min_blocksize:
             raise ValueError("sp must carry STREAMINFO's min_blocksize and max_blocksize")
-        s = stream if stream is not None else torch.cuda.current_stream()
         dev = d_bytes.device
         n = ranges_bytes.numel() // 4 if isinstance(ranges_bytes, torch.Tensor) else len(ranges_bytes)
         if not isinstance(windows, torch.Tensor):
@@ -798,13 +857,64 @@ class BatchDecoder:
             pcm_bytes = n * (nsamples + 2 * (sp.max_blocksize - 1)) * stride
             d_pcm = torch.zeros(max((pcm_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=dev)
         self.decode_parsed(d_bytes, nbytes, sel_cap, sp, fmt, d_pcm, d_sel_info, stream=s)
-        d_rows, st_gather = self.gather_ranges(d_pcm, fmt, sp, d_win, n, nsamples, stream=s)
+        return d_pcm, d_win, n, {"scan": st_scan, "index": st_index, "select": st_select}
+
+    def gather_ranges_f32(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, row_samples: int,
+                          mono: bool = False, d_out=None, plane_pitch: Optional[int] = None, stream=None, pcm_bytes=None):
+        """The windows of a decoded selection as normalised float32 channel planes
+        (bnflac_gather_ranges_f32): plane c of stream s is min(window s's nsamples, row_samples)
+        samples of channel c from its pcm_first, as sample * 2^-(bps - 1), then zeros; mono: one plane,
+        the mean of the channels.  fmt: a layout md5_layout accepts for sp (f32_layout(sp) is the
+        narrowest).  plane_pitch: floats between planes (default: row_samples); d_out: the output, a
+        float32 tensor (default: a new one); pcm_bytes: the decoded size (default: all of d_pcm).
+        -> (float32[nstreams, planes, row_samples], a view of d_out when one is passed; d_status int32[4]),
+        on the device and not synchronised."""
+        import torch
+        dev = d_pcm.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        nbytes = d_pcm.numel() * d_pcm.element_size()
+        planes = 1 if mono else sp.channels
+        pitch = row_samples if plane_pitch is None else plane_pitch
+        if pitch < row_samples:
+            raise ValueError("plane_pitch is below row_samples")
         with torch.cuda.stream(s):
-            if fmt == OUT_INTERLEAVED32:
-                rows = d_rows[: n * nsamples * stride].view(torch.int32).view(n, nsamples, sp.channels)
-            else:
-                rows = d_rows[: n * nsamples * stride].view(n, nsamples * stride)
-        return rows, {"scan": st_scan, "index": st_index, "select": st_select, "gather": st_gather}
+            if d_out is None:
+                d_out = torch.zeros(max(nstreams * planes * pitch, 1), dtype=torch.float32, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        if d_out.dtype != torch.float32 or not d_out.is_contiguous():
+            raise ValueError("d_out is a contiguous float32 tensor")
+        if nstreams and d_out.numel() < (nstreams * planes - 1) * pitch + row_samples:
+            raise ValueError("d_out is too small for nstreams * planes planes")
+        rc = self.L.bnflac_gather_ranges_f32(self.ctx, ctypes.c_void_p(d_pcm.data_ptr()),
+                                             nbytes if pcm_bytes is None else min(pcm_bytes, nbytes), fmt, ctypes.byref(sp),
+                                             ctypes.c_void_p(d_windows.data_ptr()), nstreams, row_samples, pitch,
+                                             F32_MONO if mono else 0, ctypes.c_void_p(d_out.data_ptr()),
+                                             ctypes.c_void_p(d_status.data_ptr()), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        planes_view = torch.as_strided(d_out.view(-1), (nstreams, planes, row_samples), (planes * pitch, pitch, 1))
+        return planes_view, d_status
+
+    def decode_windows_f32(self, d_bytes, nbytes: int, ranges_bytes, windows, nsamples: int, sp: StreamParams,
+                           fmt: Optional[int] = None, mono: bool = False, cap: Optional[int] = None, cand_cap: int = 0,
+                           stream=None):
+        """decode_windows with gather_ranges_f32 as its last step: nsamples sample frames from a
+        position of its own in every .flac file of a buffer, as float32 channel planes in [-1, 1),
+        with no host synchronisation and nothing read back.  Arguments, sizes and the status
+        dictionary are decode_windows' ("gather" is gather_ranges_f32's status).  fmt: the layout the
+        frames decode into, None for the narrowest one gather_ranges_f32 accepts (f32_layout(sp):
+        OUT_FLACDECODER for 16-bit streams of 1-2 channels, else OUT_FILEREADER for 16- and 24-bit
+        streams, else OUT_INTERLEAVED32).  mono: one plane per stream, the mean of the channels.
+        -> (float32[nstreams, planes, nsamples], status)"""
+        import torch
+        fmt = f32_layout(sp) if fmt is None else fmt
+        if not md5_layout(fmt, sp):
+            raise ValueError("the layout's bytes are not the samples: gather_ranges_f32 cannot read it")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        d_pcm, d_win, n, status = self._decode_selection(d_bytes, nbytes, ranges_bytes, windows, nsamples, sp, fmt, cap,
+                                                         cand_cap, s)
+        planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, n, nsamples, mono=mono, stream=s)
+        return planes, status
 
     def crc_handoff(self, nframes: int) -> np.ndarray:
         """Debug: the CRC-16 hand-off of the last parse_frames call, [nframes, 8] uint32."""

@@ -15,7 +15,8 @@
  * -> bnflac_index_streams (frames) -> bnflac_parse_frames / bnflac_decode_parsed (PCM) ->
  * bnflac_md5_streams (verification), each asynchronous on the caller's HIP stream and chained by
  * device tables.  For one sample window per stream instead of whole streams, bnflac_select_ranges
- * goes between index and decode and bnflac_gather_ranges after the decode.
+ * goes between index and decode and bnflac_gather_ranges after the decode, or
+ * bnflac_gather_ranges_f32 where the windows are wanted as float32 channel planes in [-1, 1).
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -442,6 +443,52 @@ BNFLAC_API int bnflac_gather_ranges(bnflac_ctx *ctx, const uint8_t *d_pcm, uint6
                                     const bnflac_stream_params *sp, const bnflac_window *d_windows, uint32_t nstreams,
                                     uint32_t row_samples, uint64_t row_bytes, uint8_t *d_rows, uint32_t *d_status,
                                     void *hip_stream);
+
+/* flags of bnflac_gather_ranges_f32 */
+enum { BNFLAC_F32_MONO = 1 }; /* one plane per stream: the mean of the channels */
+
+/* The windows of a decoded selection as normalised float32 channel planes: what bnflac_gather_ranges
+ * does, with the layout conversion a device-side consumer needs in the same pass.
+ * Layouts: exactly those for which bnflac_md5_layout(out_format, sp) is not 0, whose bytes are the
+ * samples themselves: BNFLAC_OUT_INTERLEAVED32 (bps 4..32; an int32 per sample), BNFLAC_OUT_FLACDECODER
+ * for 16-bit streams of 1-2 channels (an int16), BNFLAC_OUT_FILEREADER for 16- and 24-bit streams
+ * (2 or 3 little-endian bytes, sign-extended).  With stride = bnflac_out_stride(out_format, sp) and
+ * unit = stride / channels, sample (i, c) of window s is at byte (d_windows[s].pcm_first + i) *
+ * stride + c * unit of d_pcm.  Every other layout, BNFLAC_OUT_PLANAR32 among them, is refused.
+ * Values, bit for bit, with v the sample as int32 and k = 2^-(bps - 1):
+ *   per channel:  f = (float)v * k.  The int -> float conversion rounds to nearest even (exact for
+ *   |v| <= 2^24), the product with a power of two is exact, the smallest magnitude 2^-31 is normal.
+ *   BNFLAC_F32_MONO:  f = (float)((double)S * k / channels), S the int64 sum of the sample frame's
+ *   channels: an exact double product, one correctly rounded double division, one double -> float
+ *   rounding.  For one channel this is the per-channel value.
+ * Windows: the rule of bnflac_gather_ranges.  limit = pcm_bytes / stride; a window with nsamples != 0
+ * and (pcm_first > limit or nsamples > limit - pcm_first) is bad: nothing of it is read, its planes
+ * are zero, it is counted.  ncopy = min(nsamples, row_samples).  Any window table will do.
+ * Output: planes = 1 with BNFLAC_F32_MONO, else channels.  Plane c of stream s starts at d_out +
+ * (s * planes + c) * plane_pitch floats: its first ncopy floats are values, the rest up to
+ * row_samples are +0.0f, and the floats from row_samples to plane_pitch are not written.
+ * plane_pitch is any value not below row_samples (a contiguous [nstreams, planes, T] tensor with odd
+ * T will do).  d_pcm and d_out are 16-byte aligned, d_windows 8-byte aligned, d_pcm's allocation at
+ * least round_up(pcm_bytes, 16) bytes; nothing outside [0, round_up(pcm_bytes, 16)) is read.
+ * d_status (device, 4 words): [0] bit 0 some bad window, [1] how many, [2] rows cut at row_samples,
+ * [3] 0.  nstreams == 0 writes a zero status.
+ * Refused (a negative return, the cause in bnflac_last_error(), nothing launched, nothing written):
+ * a null argument as in bnflac_gather_ranges, a layout as above, channels outside 1..8, flag bits
+ * other than BNFLAC_F32_MONO, plane_pitch < row_samples, a pointer less aligned than stated,
+ * nstreams >= 2^30.
+ * No trip count or address depends on a window's contents beyond the check above.  Asynchronous on
+ * hip_stream, no host synchronisation, no allocation; the launch runs on ctx's device. */
+BNFLAC_API int bnflac_gather_ranges_f32(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int out_format,
+                                        const bnflac_stream_params *sp, const bnflac_window *d_windows, uint32_t nstreams,
+                                        uint32_t row_samples, uint64_t plane_pitch, uint32_t flags, float *d_out,
+                                        uint32_t *d_status, void *hip_stream);
+
+/* The same planes and status from host memory, by the same code (csrc/bnf_pcm_f32.h); no GPU needed.
+ * Refuses what the device call refuses apart from pointer alignment (out needs a float's).  0 or -1. */
+BNFLAC_API int bnflac_gather_ranges_f32_host(const uint8_t *pcm, uint64_t pcm_bytes, int out_format,
+                                             const bnflac_stream_params *sp, const bnflac_window *windows, uint32_t nstreams,
+                                             uint32_t row_samples, uint64_t plane_pitch, uint32_t flags, float *out,
+                                             uint32_t status[4]);
 
 /* ======================== Part 3: streaming reader ======================= */
 
