@@ -5,6 +5,9 @@
  * (bnflac_select.hip, one lane per stream) and bnflac_select_ranges_host (bnflac_runtime.cpp)
  * are the same code, as bnf_metadata.h is for the scan.  The header needs no HIP: a plain C++
  * compiler takes it too (tools/select_ranges_sanitize.cpp builds it with the sanitizers).
+ * bnflac_select_windows applies the same rule per window request, each naming its stream
+ * (bnf_select_request below: k_win_select, bnflac_select_windows_host and
+ * tools/select_windows_sanitize.cpp).
  *
  * Stream s, T = its samples, frame i of [f0, f1) at local start L_i = out_sample_i - s0 with
  * blocksize b_i:  lo = min(first_sample, T), hi = min(lo + nsamples, T) (saturating);
@@ -42,8 +45,13 @@ typedef struct {
     uint32_t skip, first_frame, nframes, flags;
 } bnf_window;
 
-enum { BNF_WIN_CLIPPED = 1u, BNF_WIN_EMPTY = 2u };          /* bnf_window.flags */
-enum { BNF_SEL_OVERFLOW = 1u, BNF_SEL_BAD_TABLES = 2u };    /* status word 0 */
+/* == bnflac_window_request */
+typedef struct {
+    uint64_t stream, first_sample, nsamples;
+} bnf_window_request;
+
+enum { BNF_WIN_CLIPPED = 1u, BNF_WIN_EMPTY = 2u, BNF_WIN_NO_STREAM = 4u };           /* bnf_window.flags */
+enum { BNF_SEL_OVERFLOW = 1u, BNF_SEL_BAD_TABLES = 2u, BNF_SEL_NO_STREAM = 4u };    /* status word 0 */
 
 /* One stream's selection before the prefixes over the streams are known. */
 typedef struct {
@@ -134,8 +142,101 @@ BNF_SEL_HD inline bnf_window bnf_select_no_window(uint32_t f0) {
     return w;
 }
 
-/* The whole call on host tables: what the three kernels of bnflac_select.hip compute.  offsets and
- * sel_offsets may be NULL. */
+/* ---- bnflac_select_windows: the same rule per window request, each naming its stream */
+enum { BNF_REQ_OK = 0, BNF_REQ_NO_STREAM = 1, BNF_REQ_BAD_SLICE = 2 };
+
+/* The window of a request when nothing is selected for it: a stream it does not name leaves
+ * first_frame 0 and no table entry read, else bnf_select_no_window of its stream. */
+BNF_SEL_HD inline bnf_window bnf_select_no_request(const uint32_t *stream_frames, uint32_t nstreams, uint64_t stream) {
+    bnf_window w = bnf_select_no_window(stream < nstreams ? stream_frames[stream] : 0u);
+    if (stream >= nstreams) w.flags |= BNF_WIN_NO_STREAM;
+    return w;
+}
+
+/* The rule for one request: bnf_select_stream over the slice of the stream it names.  A request
+ * that names no stream, or a slice that cannot be searched, reads nothing more and leaves o empty. */
+BNF_SEL_HD inline uint32_t bnf_select_request(const bnf_frame_info *info, uint32_t cap, const uint32_t *stream_frames,
+                                              const uint64_t *stream_samples, uint32_t nstreams, bnf_window_request q,
+                                              bnf_sel_stream &o) {
+    o.nsamples = o.hull = 0;
+    o.skip = o.first_frame = o.nframes = 0;
+    o.flags = BNF_WIN_EMPTY;
+    if (q.stream >= nstreams) {
+        o.flags |= BNF_WIN_NO_STREAM;
+        return BNF_REQ_NO_STREAM;
+    }
+    const uint32_t f0 = stream_frames[q.stream], f1 = stream_frames[q.stream + 1];
+    const uint64_t s0 = stream_samples[q.stream], s1 = stream_samples[q.stream + 1];
+    o.first_frame = f0;
+    if (!bnf_select_tables_ok(f0, f1, s0, s1, cap)) return BNF_REQ_BAD_SLICE;
+    bnf_sample_range r;
+    r.first_sample = q.first_sample;
+    r.nsamples = q.nsamples;
+    bnf_select_stream(info, f0, f1, s0, s1, r, o);
+    return BNF_REQ_OK;
+}
+
+/* A frame prefix as the 32-bit tables hold it */
+BNF_SEL_HD inline uint32_t bnf_sel_sat32(uint64_t frames) {
+    return frames > 0xffffffffull ? 0xffffffffu : (uint32_t)frames;
+}
+
+/* The whole bnflac_select_windows call on host tables: what k_win_select / k_win_scan /
+ * k_win_apply / k_sel_emit compute.  offsets and sel_offsets may be NULL. */
+inline void bnf_select_windows_host(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
+                                    const uint32_t *stream_frames, const uint64_t *stream_samples, uint32_t nstreams,
+                                    const bnf_window_request *requests, uint32_t nwindows, uint64_t *sel_offsets,
+                                    bnf_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames, uint64_t *sel_samples,
+                                    bnf_window *windows, uint32_t status[4]) {
+    bool bad = false, no_stream = false;
+    for (uint32_t w = 0; w < nwindows; w++) { /* only the slices some request names are judged */
+        const uint64_t t = requests[w].stream;
+        if (t >= nstreams)
+            no_stream = true;
+        else
+            bad = bad || !bnf_select_tables_ok(stream_frames[t], stream_frames[t + 1], stream_samples[t], stream_samples[t + 1], cap);
+    }
+    uint64_t nf = 0, ns = 0; /* the frame total is not bounded by cap: windows may share frames */
+    uint32_t nonempty = 0, clipped = 0;
+    for (uint32_t w = 0; w < nwindows; w++) {
+        sel_frames[w] = bnf_sel_sat32(nf);
+        sel_samples[w] = ns;
+        if (bad) {
+            windows[w] = bnf_select_no_request(stream_frames, nstreams, requests[w].stream);
+            continue;
+        }
+        bnf_sel_stream o;
+        bnf_select_request(info, cap, stream_frames, stream_samples, nstreams, requests[w], o);
+        windows[w] = bnf_select_window(o, ns);
+        const uint64_t first = o.nframes ? info[o.first_frame].out_sample : 0;
+        for (uint32_t k = 0; k < o.nframes; k++) {
+            const uint64_t p = nf + k;
+            if (p >= sel_cap) break;
+            sel_info[p] = info[o.first_frame + k];
+            sel_info[p].out_sample = ns + (info[o.first_frame + k].out_sample - first);
+            if (sel_offsets) sel_offsets[p] = offsets ? offsets[o.first_frame + k] : 0;
+        }
+        nf += o.nframes;
+        ns += o.hull;
+        nonempty += (o.flags & BNF_WIN_EMPTY) ? 0u : 1u;
+        clipped += (o.flags & BNF_WIN_CLIPPED) ? 1u : 0u;
+    }
+    sel_frames[nwindows] = bnf_sel_sat32(nf);
+    sel_samples[nwindows] = ns;
+    for (uint64_t p = nf; p < sel_cap; p++) { /* filler: zeros, skipped, no error */
+        memset(&sel_info[p], 0, sizeof sel_info[p]);
+        sel_info[p].status = BNF_ST_SKIPPED;
+        sel_info[p].err = -1;
+        if (sel_offsets) sel_offsets[p] = 0;
+    }
+    status[0] = (bad ? BNF_SEL_BAD_TABLES : nf > sel_cap ? BNF_SEL_OVERFLOW : 0u) | (no_stream ? BNF_SEL_NO_STREAM : 0u);
+    status[1] = bnf_sel_sat32(nf);
+    status[2] = nonempty;
+    status[3] = clipped;
+}
+
+/* The whole bnflac_select_ranges call on host tables: what the k_sel_* kernels of bnflac_select.hip
+ * compute.  offsets and sel_offsets may be NULL. */
 inline void bnf_select_ranges_host(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
                                    const uint32_t *stream_frames, const uint64_t *stream_samples, uint32_t nstreams,
                                    const bnf_sample_range *ranges, uint64_t *sel_offsets, bnf_frame_info *sel_info,

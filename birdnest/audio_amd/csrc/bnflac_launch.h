@@ -228,6 +228,14 @@ hipError_t bnf_launch_select_ranges(const uint64_t *offsets, const bnf_frame_inf
                                     uint64_t *sel_offsets, bnf_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames,
                                     uint64_t *sel_samples, bnf_window *windows, uint32_t *status, void *scratch,
                                     hipStream_t s);
+/* k_win_*: the same selection per window request (bnf_select_request), outputs sized by nwindows.
+ * scratch: bnf_select_windows_scratch_bytes(nwindows) bytes, 16-byte aligned.  Writes every status word. */
+uint64_t bnf_select_windows_scratch_bytes(uint32_t nwindows);
+hipError_t bnf_launch_select_windows(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap, const uint32_t *sf,
+                                     const uint64_t *ss, uint32_t nstreams, const bnf_window_request *requests,
+                                     uint32_t nwindows, uint64_t *sel_offsets, bnf_frame_info *sel_info, uint32_t sel_cap,
+                                     uint32_t *sel_frames, uint64_t *sel_samples, bnf_window *windows, uint32_t *status,
+                                     void *scratch, hipStream_t s);
 /* k_gather_ranges: row s = rows + s * row_bytes gets min(windows[s].nsamples, row_samples) sample
  * frames of `stride` bytes from pcm + windows[s].pcm_first * stride, then zeros up to row_samples
  * frames.  pcm 16-byte aligned, its allocation at least round_up(pcm_bytes, 16) bytes.  Zeroes

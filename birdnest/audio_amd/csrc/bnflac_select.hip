@@ -1,6 +1,7 @@
 /*
  * bnflac_select.hip -- sample windows of a batch: k_sel_streams / k_sel_scan / k_sel_apply /
- * k_sel_emit (bnflac_select_ranges) cut the index of bnflac_index_streams down to the frames the
+ * k_sel_emit (bnflac_select_ranges) and k_win_select / k_win_scan / k_win_apply
+ * (bnflac_select_windows) cut the index of bnflac_index_streams down to the frames the
  * windows need, k_gather_ranges (bnflac_gather_ranges) copies the decoded windows into rows of
  * one shape.  No CRC tables, no g_stats, no ablate word.
  *
@@ -21,6 +22,14 @@
  *                  the filler record.  Nothing at or past sel_cap is written.
  * Loop bounds: the searches of bnf_select.h run over index intervals, the emit's search over
  * [0, nstreams]; no trip count is a table value.  A source position is checked against cap.
+ *
+ * Selection per window request (bnflac_select_windows): the same four launches with one lane per
+ * window, k_win_select / k_win_scan / k_win_apply and k_sel_emit itself.  A lane loads its request,
+ * checks the stream it names against nstreams and reads that stream's four table entries; no grid,
+ * loop bound or scratch size depends on nstreams.  Windows may share frames, so frame counts are
+ * scanned in 64 bits: k_win_select leaves each window's prefix inside its workgroup in the scratch,
+ * k_win_apply adds the workgroup's base and writes min(prefix, UINT32_MAX).  The emit compares a
+ * position below sel_cap with prefix entries only, and a saturated entry is above every position.
  *
  * Gather.  Row s = min(nsamples, row_samples) sample frames from pcm_first, then zeros up to
  * row_samples.  Source offset (pcm_first * stride) and destination offset (s * row_bytes) have
@@ -44,18 +53,20 @@
 #define SEL_WAVES (SEL_BLOCK / 64)
 
 static_assert(sizeof(bnf_frame_info) == 128 && sizeof(bnf_window) == 32 && sizeof(bnf_sample_range) == 16, "record sizes");
+static_assert(sizeof(bnf_window_request) == 24, "request size");
 
-/* Exclusive scan of (f, s) over the workgroup's SEL_BLOCK lanes; tf / ts: the workgroup's sums. */
-__device__ __forceinline__ void sel_block_scan(uint32_t f, uint64_t s, uint32_t &ef, uint64_t &es, uint32_t &tf,
-                                               uint64_t &ts) {
-    __shared__ uint32_t wf[SEL_WAVES];
+/* Exclusive scan of (f, s) over the workgroup's SEL_BLOCK lanes; tf / ts: the workgroup's sums.
+ * F: uint32_t for frames per stream (bounded by cap), uint64_t for frames per window (not bounded). */
+template <typename F>
+__device__ __forceinline__ void sel_block_scan(F f, uint64_t s, F &ef, uint64_t &es, F &tf, uint64_t &ts) {
+    __shared__ F wf[SEL_WAVES];
     __shared__ uint64_t ws[SEL_WAVES];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t cf = f;
+    F cf = f;
     uint64_t cs = s;
 #pragma unroll
     for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t uf = __shfl_up(cf, d);
+        const F uf = __shfl_up(cf, d);
         const uint64_t us = __shfl_up(cs, d);
         if (lane >= d) {
             cf += uf;
@@ -68,7 +79,7 @@ __device__ __forceinline__ void sel_block_scan(uint32_t f, uint64_t s, uint32_t 
         ws[wave] = cs;
     }
     __syncthreads();
-    uint32_t bf = 0;
+    F bf = 0;
     uint64_t bs = 0;
     tf = 0;
     ts = 0;
@@ -250,6 +261,134 @@ extern "C" hipError_t bnf_launch_select_ranges(const uint64_t *offsets, const bn
         const uint64_t threads = 8ull * sel_cap;
         hipLaunchKernelGGL(k_sel_emit, dim3((uint32_t)((threads + EMIT_THREADS - 1) / EMIT_THREADS)), dim3(EMIT_THREADS), 0, s,
                            offsets, info, cap, sel_frames, sel_samples, nstreams, windows, sel_offsets, sel_info, sel_cap);
+    }
+    return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ selection per window request */
+/* ctl: [0] bad flag, [1] windows that are not empty, [2] windows clipped, [3] a request names no stream.
+ * rel_frames: the window's frame prefix inside its workgroup, in 64 bits (k_win_apply saturates). */
+__global__ __launch_bounds__(SEL_BLOCK) void k_win_select(const bnf_frame_info *__restrict__ info, uint32_t cap,
+                                                          const uint32_t *__restrict__ sf, const uint64_t *__restrict__ ss,
+                                                          uint32_t nstreams, const bnf_window_request *__restrict__ requests,
+                                                          uint32_t nwindows, uint64_t *__restrict__ rel_frames,
+                                                          uint64_t *__restrict__ sel_samples, bnf_window *__restrict__ windows,
+                                                          uint32_t *__restrict__ ctl, uint64_t *__restrict__ wg_frames,
+                                                          uint64_t *__restrict__ wg_samples) {
+    const uint32_t w = blockIdx.x * SEL_BLOCK + threadIdx.x;
+    const bool live = w < nwindows;
+    bnf_sel_stream o;
+    o.nsamples = o.hull = 0;
+    o.skip = o.first_frame = o.nframes = 0;
+    o.flags = BNF_WIN_EMPTY;
+    uint32_t verdict = BNF_REQ_OK;
+    if (live) verdict = bnf_select_request(info, cap, sf, ss, nstreams, requests[w], o);
+    uint64_t ef, tf, es, ts;
+    sel_block_scan<uint64_t>(o.nframes, o.hull, ef, es, tf, ts);
+    if (live) {
+        rel_frames[w] = ef;
+        sel_samples[w] = es;
+        windows[w] = bnf_select_window(o, es);
+    }
+    if (threadIdx.x == 0) {
+        wg_frames[blockIdx.x] = tf;
+        wg_samples[blockIdx.x] = ts;
+    }
+    const bool any_bad = __ballot(verdict == BNF_REQ_BAD_SLICE) != 0;
+    const bool any_none = __ballot(verdict == BNF_REQ_NO_STREAM) != 0;
+    const uint32_t nonempty = (uint32_t)__popcll(__ballot(live && !(o.flags & BNF_WIN_EMPTY)));
+    const uint32_t clipped = (uint32_t)__popcll(__ballot(live && (o.flags & BNF_WIN_CLIPPED)));
+    if ((threadIdx.x & 63u) == 0) {
+        if (any_bad) atomicOr(&ctl[0], 1u);
+        if (nonempty) atomicAdd(&ctl[1], nonempty);
+        if (clipped) atomicAdd(&ctl[2], clipped);
+        if (any_none) atomicOr(&ctl[3], 1u);
+    }
+}
+
+/* One workgroup: the workgroup sums become their exclusive prefixes; totals (frames saturating) and status. */
+__global__ __launch_bounds__(SEL_BLOCK) void k_win_scan(uint64_t *__restrict__ wg_frames, uint64_t *__restrict__ wg_samples,
+                                                        uint32_t nwg, uint32_t nwindows, uint32_t sel_cap,
+                                                        const uint32_t *__restrict__ ctl, uint32_t *__restrict__ sel_frames,
+                                                        uint64_t *__restrict__ sel_samples, uint32_t *__restrict__ status) {
+    uint64_t carry_f = 0, carry_s = 0;
+    for (uint32_t base = 0; base < nwg; base += SEL_BLOCK) {
+        const uint32_t i = base + threadIdx.x;
+        const uint64_t f = i < nwg ? wg_frames[i] : 0u;
+        const uint64_t s = i < nwg ? wg_samples[i] : 0u;
+        uint64_t ef, tf, es, ts;
+        sel_block_scan<uint64_t>(f, s, ef, es, tf, ts);
+        if (i < nwg) {
+            wg_frames[i] = carry_f + ef;
+            wg_samples[i] = carry_s + es;
+        }
+        carry_f += tf;
+        carry_s += ts;
+    }
+    if (threadIdx.x == 0) {
+        const bool bad = ctl[0] != 0;
+        const uint32_t none = ctl[3] ? BNF_SEL_NO_STREAM : 0u;
+        sel_frames[nwindows] = bad ? 0u : bnf_sel_sat32(carry_f);
+        sel_samples[nwindows] = bad ? 0u : carry_s;
+        status[0] = (bad ? BNF_SEL_BAD_TABLES : carry_f > sel_cap ? BNF_SEL_OVERFLOW : 0u) | none;
+        status[1] = bad ? 0u : bnf_sel_sat32(carry_f);
+        status[2] = bad ? 0u : ctl[1];
+        status[3] = bad ? 0u : ctl[2];
+    }
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_win_apply(const uint32_t *__restrict__ sf, uint32_t nstreams,
+                                                         const bnf_window_request *__restrict__ requests, uint32_t nwindows,
+                                                         const uint64_t *__restrict__ rel_frames,
+                                                         const uint64_t *__restrict__ wg_frames,
+                                                         const uint64_t *__restrict__ wg_samples, const uint32_t *__restrict__ ctl,
+                                                         uint32_t *__restrict__ sel_frames, uint64_t *__restrict__ sel_samples,
+                                                         bnf_window *__restrict__ windows) {
+    const uint32_t w = blockIdx.x * SEL_BLOCK + threadIdx.x;
+    if (w >= nwindows) return;
+    if (ctl[0]) {
+        sel_frames[w] = 0;
+        sel_samples[w] = 0;
+        windows[w] = bnf_select_no_request(sf, nstreams, requests[w].stream);
+    } else {
+        sel_frames[w] = bnf_sel_sat32(wg_frames[blockIdx.x] + rel_frames[w]);
+        sel_samples[w] += wg_samples[blockIdx.x];
+        windows[w].pcm_first += wg_samples[blockIdx.x];
+    }
+}
+
+extern "C" uint64_t bnf_select_windows_scratch_bytes(uint32_t nwindows) {
+    const uint64_t nwg = ((uint64_t)nwindows + SEL_BLOCK - 1) / SEL_BLOCK;
+    return 16u + 16u * nwg + 8u * (uint64_t)nwindows;
+}
+
+/* The emit is k_sel_emit: its inputs mean the same with a window in a stream's place, and it only
+ * compares positions below sel_cap with prefix entries, which saturation leaves in order. */
+extern "C" hipError_t bnf_launch_select_windows(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
+                                                const uint32_t *sf, const uint64_t *ss, uint32_t nstreams,
+                                                const bnf_window_request *requests, uint32_t nwindows, uint64_t *sel_offsets,
+                                                bnf_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames,
+                                                uint64_t *sel_samples, bnf_window *windows, uint32_t *status, void *scratch,
+                                                hipStream_t s) {
+    const uint32_t nwg = (uint32_t)(((uint64_t)nwindows + SEL_BLOCK - 1) / SEL_BLOCK);
+    uint32_t *ctl = (uint32_t *)scratch;
+    uint64_t *wg_frames = (uint64_t *)((uint8_t *)scratch + 16u);
+    uint64_t *wg_samples = wg_frames + nwg;
+    uint64_t *rel_frames = wg_samples + nwg;
+    hipError_t e = hipMemsetAsync(ctl, 0, 16, s);
+    if (e != hipSuccess) return e;
+    if (nwg)
+        hipLaunchKernelGGL(k_win_select, dim3(nwg), dim3(SEL_BLOCK), 0, s, info, cap, sf, ss, nstreams, requests, nwindows,
+                           rel_frames, sel_samples, windows, ctl, wg_frames, wg_samples);
+    hipLaunchKernelGGL(k_win_scan, dim3(1), dim3(SEL_BLOCK), 0, s, wg_frames, wg_samples, nwg, nwindows, sel_cap, ctl,
+                       sel_frames, sel_samples, status);
+    if (nwg)
+        hipLaunchKernelGGL(k_win_apply, dim3(nwg), dim3(SEL_BLOCK), 0, s, sf, nstreams, requests, nwindows, rel_frames,
+                           wg_frames, wg_samples, ctl, sel_frames, sel_samples, windows);
+    if (sel_cap) {
+        const uint64_t threads = 8ull * sel_cap;
+        hipLaunchKernelGGL(k_sel_emit, dim3((uint32_t)((threads + EMIT_THREADS - 1) / EMIT_THREADS)), dim3(EMIT_THREADS), 0, s,
+                           offsets, info, cap, sel_frames, sel_samples, nwindows, windows, sel_offsets, sel_info, sel_cap);
     }
     return hipGetLastError();
 }

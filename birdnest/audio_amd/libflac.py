@@ -129,6 +129,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_index_streams", "bnflac_md5_layout", "bnflac_md5_streams",
                  "bnflac_scan_streams", "bnflac_scan_stream_host",
                  "bnflac_select_ranges", "bnflac_select_ranges_host", "bnflac_gather_ranges",
+                 "bnflac_select_windows", "bnflac_select_windows_host",
                  "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
@@ -227,6 +228,12 @@ def load() -> ctypes.CDLL:
                                        p, p]
     L.bnflac_select_ranges_host.restype = i
     L.bnflac_select_ranges_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, p, p]
+    L.bnflac_select_windows.restype = i
+    L.bnflac_select_windows.argtypes = [p, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, ctypes.c_uint32, p, p,
+                                        ctypes.c_uint32, p, p, p, p, p]
+    L.bnflac_select_windows_host.restype = i
+    L.bnflac_select_windows_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, ctypes.c_uint32, p,
+                                             ctypes.c_uint32, p, p, p, p]
     L.bnflac_gather_ranges.restype = i
     L.bnflac_gather_ranges.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                        p, p, p]
@@ -404,14 +411,21 @@ class Window(ctypes.Structure):
                 ("first_frame", ctypes.c_uint32), ("nframes", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class WindowRequest(ctypes.Structure):
+    """bnflac_window_request: one crop of select_windows, a window of the stream it names."""
+    _fields_ = [("stream", ctypes.c_uint64), ("first_sample", ctypes.c_uint64), ("nsamples", ctypes.c_uint64)]
+
+
 SAMPLE_RANGE_DTYPE = np.dtype([("first_sample", "<u8"), ("nsamples", "<u8")])
+WINDOW_REQUEST_DTYPE = np.dtype([("stream", "<u8"), ("first_sample", "<u8"), ("nsamples", "<u8")])
 WINDOW_BYTES = 32
 WINDOW_DTYPE = np.dtype([("pcm_first", "<u8"), ("nsamples", "<u8"), ("skip", "<u4"), ("first_frame", "<u4"),
                          ("nframes", "<u4"), ("flags", "<u4")])
 assert SAMPLE_RANGE_DTYPE.itemsize == ctypes.sizeof(SampleRange) == 16
 assert WINDOW_DTYPE.itemsize == ctypes.sizeof(Window) == WINDOW_BYTES
-WIN_CLIPPED, WIN_EMPTY = 1, 2          # Window.flags
-SEL_OVERFLOW, SEL_BAD_TABLES = 1, 2    # select_ranges status word 0
+assert WINDOW_REQUEST_DTYPE.itemsize == ctypes.sizeof(WindowRequest) == 24
+WIN_CLIPPED, WIN_EMPTY, WIN_NO_STREAM = 1, 2, 4           # Window.flags (WIN_NO_STREAM: select_windows only)
+SEL_OVERFLOW, SEL_BAD_TABLES, SEL_NO_STREAM = 1, 2, 4     # select_ranges / select_windows status word 0
 TO_THE_END = (1 << 64) - 1             # SampleRange.nsamples: up to the stream's end
 
 
@@ -450,6 +464,44 @@ def select_ranges_host(info: np.ndarray, cap: int, stream_frames, stream_samples
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
     rc = load().bnflac_select_ranges_host(vp(info), cap, vp(sf), vp(ss), n, vp(r), vp(sel), sel_cap, vp(sel_f), vp(sel_s),
                                           vp(win), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return sel, sel_f, sel_s, win, status
+
+
+def window_requests(reqs) -> np.ndarray:
+    """[(stream, first_sample[, nsamples])] -> the table of select_windows (WINDOW_REQUEST_DTYPE);
+    nsamples defaults to TO_THE_END."""
+    table = np.zeros(len(reqs), dtype=WINDOW_REQUEST_DTYPE)
+    for k, r in enumerate(reqs):
+        r = tuple(r) if len(r) == 3 else (r[0], r[1], TO_THE_END)
+        if not all(0 <= x <= TO_THE_END for x in r):
+            raise ValueError(f"window {k}: a request is three unsigned 64-bit numbers")
+        table[k] = r
+    return table
+
+
+def select_windows_host(info: np.ndarray, cap: int, stream_frames, stream_samples, requests, sel_cap: int):
+    """select_windows over host tables (bnflac_select_windows_host, no GPU).  info: FRAME_INFO_DTYPE
+    records (at least the ones below cap that a request's stream holds); requests:
+    [(stream, first_sample[, nsamples])] or a WINDOW_REQUEST_DTYPE array, any number per stream.
+    -> (sel_info[sel_cap], sel_frames uint32[k+1], sel_samples uint64[k+1], windows[k], status uint32[4])
+    for k requests, in their order."""
+    info = np.ascontiguousarray(info, dtype=FRAME_INFO_DTYPE)
+    sf = np.ascontiguousarray(stream_frames, dtype=np.uint32)
+    ss = np.ascontiguousarray(stream_samples, dtype=np.uint64)
+    n = len(sf) - 1
+    if n < 0 or len(ss) != n + 1 or len(info) < min(cap, int(sf.max(initial=0))):
+        raise ValueError("stream_frames and stream_samples hold nstreams + 1 entries, info the records below cap")
+    r = requests if isinstance(requests, np.ndarray) and requests.dtype == WINDOW_REQUEST_DTYPE else window_requests(requests)
+    r = np.ascontiguousarray(r)
+    k = len(r)
+    sel = np.zeros(sel_cap, dtype=FRAME_INFO_DTYPE)
+    sel_f, sel_s = np.zeros(k + 1, np.uint32), np.zeros(k + 1, np.uint64)
+    win, status = np.zeros(k, dtype=WINDOW_DTYPE), np.zeros(4, np.uint32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    rc = load().bnflac_select_windows_host(vp(info), cap, vp(sf), vp(ss), n, vp(r), k, vp(sel), sel_cap, vp(sel_f),
+                                           vp(sel_s), vp(win), vp(status))
     if rc != 0:
         raise RuntimeError(load().bnflac_last_error().decode())
     return sel, sel_f, sel_s, win, status
@@ -538,6 +590,20 @@ def streaminfo_md5(data) -> bytes:
     if len(data) < 42 or data[:4] != b"fLaC" or data[4] & 0x7F != 0:
         raise ValueError("not a FLAC stream that starts with a STREAMINFO block")
     return data[26:42]
+
+
+class Corpus:
+    """A batch of .flac files indexed once (BatchDecoder.index_corpus) and kept on the device:
+    what decode_crops needs to cut any number of batches of crops out of it.  Nothing in it is
+    written after index_corpus, so work that uses it only has to be ordered after that call (the
+    same stream, or the caller's events)."""
+
+    def __init__(self, d_bytes, nbytes, sp, nstreams, cap, d_offsets, d_info, d_stream_frames, d_stream_samples,
+                 scan_status, index_status):
+        self.d_bytes, self.nbytes, self.sp, self.nstreams, self.cap = d_bytes, nbytes, sp, nstreams, cap
+        self.d_offsets, self.d_info = d_offsets, d_info
+        self.d_stream_frames, self.d_stream_samples = d_stream_frames, d_stream_samples
+        self.scan_status, self.index_status = scan_status, index_status  # device int32[4] each, not synchronised
 
 
 class BatchDecoder:
@@ -772,6 +838,46 @@ class BatchDecoder:
             raise RuntimeError(self.L.bnflac_last_error().decode())
         return d_sel_offs, d_sel_info, d_sel_f, d_sel_s, d_win, d_status
 
+    def select_windows(self, d_offsets, d_info, cap: int, d_stream_frames, d_stream_samples, nstreams: int, requests,
+                       sel_cap: int, stream=None):
+        """Cut index_streams' tables down to the frames any crops of the batch need
+        (bnflac_select_windows): select_ranges with one output row per request instead of per stream.
+        requests: [(stream, first_sample[, nsamples])], any number per stream in any order, or the
+        same on the device (a contiguous 64-bit tensor of 3 words per window).  The tables are only
+        read.
+        -> (d_sel_offsets int64[sel_cap], d_sel_info uint8[sel_cap*128] ready for
+            decode_parsed(nframes=sel_cap), d_sel_frames int32[k+1], d_sel_samples int64[k+1],
+            d_windows uint8[k*32] for gather_ranges(nstreams=k), d_status int32[4]) for k requests,
+        all on the device and not synchronised, like select_ranges."""
+        import torch
+        dev = d_info.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        on_device = isinstance(requests, torch.Tensor)
+        if on_device:
+            if not requests.is_cuda or requests.element_size() != 8 or requests.numel() % 3 or not requests.is_contiguous():
+                raise ValueError("device requests are a contiguous CUDA tensor of 3 64-bit words per window")
+            d_req, k = requests, requests.numel() // 3
+        else:
+            table = window_requests(requests)
+            k = len(table)
+        with torch.cuda.stream(s):
+            if not on_device:
+                d_req = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev) if k else None
+            d_sel_offs = torch.zeros(max(sel_cap, 1), dtype=torch.int64, device=dev)
+            d_sel_info = torch.zeros(max(sel_cap, 1) * FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
+            d_sel_f = torch.zeros(k + 1, dtype=torch.int32, device=dev)
+            d_sel_s = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+            d_win = torch.zeros(max(k, 1) * WINDOW_BYTES, dtype=torch.uint8, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self.L.bnflac_select_windows(self.ctx, vp(d_offsets), vp(d_info), cap, vp(d_stream_frames),
+                                          vp(d_stream_samples), nstreams, vp(d_req) if k else None, k,
+                                          vp(d_sel_offs) if d_offsets is not None else None, vp(d_sel_info), sel_cap,
+                                          vp(d_sel_f), vp(d_sel_s), vp(d_win), vp(d_status), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_sel_offs, d_sel_info, d_sel_f, d_sel_s, d_win, d_status
+
     def gather_ranges(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, row_samples: int,
                       row_bytes: Optional[int] = None, d_rows=None, stream=None, pcm_bytes=None):
         """The windows of a decoded selection as rows of one shape (bnflac_gather_ranges): row s is
@@ -914,6 +1020,92 @@ class BatchDecoder:
         d_pcm, d_win, n, status = self._decode_selection(d_bytes, nbytes, ranges_bytes, windows, nsamples, sp, fmt, cap,
                                                          cand_cap, s)
         planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, n, nsamples, mono=mono, stream=s)
+        return planes, status
+
+    def index_corpus(self, d_bytes, nbytes: int, ranges_bytes, sp: StreamParams, cap: Optional[int] = None,
+                     cand_cap: int = 0, stream=None) -> Corpus:
+        """scan_streams -> index_streams over the .flac files of a buffer, once, for any number of
+        decode_crops / decode_crops_f32 calls.  Arguments as for decode_windows (cap defaults to
+        nbytes // 16 + 16); nothing is synchronised or read back.  The caller keeps d_bytes alive and
+        unchanged as long as the Corpus is used, and orders that use after this call (the same
+        stream, or events)."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        n = ranges_bytes.numel() // 4 if isinstance(ranges_bytes, torch.Tensor) else len(ranges_bytes)
+        cap = nbytes // 16 + 16 if cap is None else cap
+        d_tab, _, _, st_scan = self.scan_streams(d_bytes, nbytes, ranges_bytes, expect=sp, stream=s)
+        d_offs, _, d_info, d_sf, d_ss, st_index = self.index_streams(d_bytes, nbytes, d_tab, sp, cap, cand_cap=cand_cap,
+                                                                     stream=s)
+        return Corpus(d_bytes, nbytes, sp, n, cap, d_offs, d_info, d_sf, d_ss, st_scan, st_index)
+
+    def _decode_crop_selection(self, corpus: Corpus, requests, nsamples, fmt, s):
+        """The front of decode_crops and decode_crops_f32: select_windows over the corpus's index ->
+        decode_parsed(nframes = sel_cap) of the copied records into a compact PCM in fmt, on stream s.
+        -> (d_pcm, d_windows, nwindows, {"select" -> int32[4]})"""
+        import torch
+        sp = corpus.sp
+        if nsamples < 1:
+            raise ValueError("nsamples must be at least 1")
+        if fmt == OUT_PLANAR32:
+            raise ValueError("OUT_PLANAR32 is channel-major per frame: a window of it is no byte range")
+        if sp.min_blocksize < 1 or sp.max_blocksize < sp.min_blocksize:
+            raise ValueError("sp must carry STREAMINFO's min_blocksize and max_blocksize")
+        if isinstance(requests, torch.Tensor):
+            k = requests.numel() // 3
+        else:
+            requests = [(r[0], r[1], nsamples) if len(r) == 2 else tuple(r) for r in requests]
+            k = len(requests)
+        sel_cap = k * ((nsamples - 1) // sp.min_blocksize + 2)
+        stride = out_stride(fmt, sp)
+        _, d_sel_info, _, _, d_win, st_select = self.select_windows(corpus.d_offsets, corpus.d_info, corpus.cap,
+                                                                    corpus.d_stream_frames, corpus.d_stream_samples,
+                                                                    corpus.nstreams, requests, sel_cap, stream=s)
+        with torch.cuda.stream(s):
+            pcm_bytes = k * (nsamples + 2 * (sp.max_blocksize - 1)) * stride
+            d_pcm = torch.zeros(max((pcm_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=corpus.d_bytes.device)
+        self.decode_parsed(corpus.d_bytes, corpus.nbytes, sel_cap, sp, fmt, d_pcm, d_sel_info, stream=s)
+        return d_pcm, d_win, k, {"select": st_select}
+
+    def decode_crops(self, corpus: Corpus, requests, nsamples: int, fmt: int, stream=None):
+        """Any crops of nsamples sample frames out of an indexed corpus, as rows in request order:
+        select_windows -> decode_parsed(nframes = sel_cap) -> gather_ranges over the index that
+        index_corpus made, with no host synchronisation and nothing read back.
+        requests: [(stream, first_sample)] or [(stream, first_sample, n)] with n <= nsamples, any
+        number per stream (a frame two crops share is decoded twice), or a device tensor of 3 64-bit
+        words per crop; a stream id that is not in the corpus gives a zero row and bit 2 of the
+        select status.  Sizes are decode_windows' with the crops in the streams' place: sel_cap =
+        k * ((nsamples - 1) // min_blocksize + 2) records, a compact PCM of
+        k * (nsamples + 2 * (max_blocksize - 1)) sample frames.  The decode completes the copied
+        records, never the corpus's, so one corpus serves any number of calls; each must be ordered
+        after index_corpus (the same stream, or the caller's events).
+        -> (rows, status): rows int32[k, nsamples, channels] for OUT_INTERLEAVED32, else
+        uint8[k, nsamples * stride]; status: {"select", "gather"} -> device int32[4]."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        sp = corpus.sp
+        d_pcm, d_win, k, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s)
+        stride = out_stride(fmt, sp)
+        d_rows, status["gather"] = self.gather_ranges(d_pcm, fmt, sp, d_win, k, nsamples, stream=s)
+        with torch.cuda.stream(s):
+            if fmt == OUT_INTERLEAVED32:
+                rows = d_rows[: k * nsamples * stride].view(torch.int32).view(k, nsamples, sp.channels)
+            else:
+                rows = d_rows[: k * nsamples * stride].view(k, nsamples * stride)
+        return rows, status
+
+    def decode_crops_f32(self, corpus: Corpus, requests, nsamples: int, fmt: Optional[int] = None, mono: bool = False,
+                         stream=None):
+        """decode_crops with gather_ranges_f32 as its last step: the crops as float32 channel planes
+        in [-1, 1), in request order.  fmt, mono: as for decode_windows_f32.
+        -> (float32[k, planes, nsamples], status)"""
+        import torch
+        sp = corpus.sp
+        fmt = f32_layout(sp) if fmt is None else fmt
+        if not md5_layout(fmt, sp):
+            raise ValueError("the layout's bytes are not the samples: gather_ranges_f32 cannot read it")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        d_pcm, d_win, k, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s)
+        planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, k, nsamples, mono=mono, stream=s)
         return planes, status
 
     def crc_handoff(self, nframes: int) -> np.ndarray:

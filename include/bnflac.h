@@ -17,6 +17,8 @@
  * device tables.  For one sample window per stream instead of whole streams, bnflac_select_ranges
  * goes between index and decode and bnflac_gather_ranges after the decode, or
  * bnflac_gather_ranges_f32 where the windows are wanted as float32 channel planes in [-1, 1).
+ * For any crops of a batch that stays resident (several of one stream, none of most, in the
+ * sampler's order), bnflac_select_windows takes bnflac_select_ranges' place over an index made once.
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -427,6 +429,72 @@ BNFLAC_API int bnflac_select_ranges_host(const bnflac_frame_info *info, uint32_t
                                          const bnflac_sample_range *ranges, bnflac_frame_info *sel_info, uint32_t sel_cap,
                                          uint32_t *sel_frames, uint64_t *sel_samples, bnflac_window *windows,
                                          uint32_t status[4]);
+
+/* One crop of bnflac_select_windows: a sample window of stream `stream` of the index's tables. */
+typedef struct {
+    uint64_t stream;                 /* position in the index's tables; >= nstreams: no such stream */
+    uint64_t first_sample, nsamples; /* as bnflac_sample_range */
+} bnflac_window_request;             /* 24 bytes, 8-byte aligned: 3 64-bit words, a [nwindows, 3] int64 tensor */
+
+enum { BNFLAC_WIN_NO_STREAM = 4 };   /* bnflac_window.flags bit 2, only written by bnflac_select_windows */
+
+/* bnflac_select_ranges with the window as its unit: any crops of an indexed batch, in the order
+ * they are asked for.  Each of the nwindows requests names the stream it wants a piece of; any
+ * number may name the same stream, in any order, and a stream nobody names costs nothing.  The
+ * tables (d_frame_offsets, d_info, cap, d_stream_frames, d_stream_samples, nstreams) are one earlier
+ * bnflac_index_streams call's and are only read, so one index serves any number of calls: per batch
+ * the chain is bnflac_select_windows -> bnflac_decode_parsed(nframes = sel_cap) ->
+ * bnflac_gather_ranges / bnflac_gather_ranges_f32 with nstreams = nwindows.
+ * Per window w, with t = d_requests[w].stream: t >= nstreams gives an empty window with flags bit 1
+ * and bit 2 (first_frame 0, nframes 0, skip 0, nsamples 0), and no table entry is read for it.
+ * Otherwise the window is bnflac_select_ranges' rule over stream t's slice of the tables with
+ * (first_sample, nsamples): the same lo and hi, saturating sum, clipping flag, "a frame that only
+ * touches is not selected", and skip.
+ * The outputs are per window, in request order.  d_sel_frames and d_sel_samples (nwindows + 1
+ * entries each) are the exclusive prefixes of the frames and hull samples selected per window;
+ * window w owns the sample frames [d_sel_samples[w], d_sel_samples[w + 1]) of the compact PCM,
+ * pcm_first = d_sel_samples[w] + skip, and its records are the selected records copied byte for
+ * byte apart from out_sample = d_sel_samples[w] + (L_i - L_a).  Two windows on one stream each get
+ * their own copy of the frames they need: a frame both need is copied and decoded twice, nothing
+ * is deduplicated.  Positions [total, sel_cap) are filler records, as for bnflac_select_ranges.
+ * So the frame total is not bounded by cap.  Frames are counted in 64 bits, and d_sel_frames and
+ * status word 1 hold min(prefix, UINT32_MAX); a saturated total exceeds every sel_cap (bit 0), and
+ * the records below sel_cap are exactly right, since they only depend on prefix entries <= their
+ * position.  Sample prefixes are modulo 2^64, as all sample arithmetic here.
+ * d_status (device, 4 words): [0] bit 0 more frames selected than sel_cap, bit 1 unusable tables,
+ * bit 2 some request names no stream; [1] frames selected (saturating); [2] windows that are not
+ * empty; [3] windows clipped.  Unusable is judged only on the slices some request names
+ * (d_stream_frames[t] <= d_stream_frames[t + 1] <= cap, d_stream_samples[t] <= d_stream_samples[t + 1]):
+ * a bad slice nobody names is not read and is no error.  If a named slice is bad, nothing is
+ * selected, as for bnflac_select_ranges: both prefix tables are zero, every record below sel_cap is
+ * filler, words 1-3 are 0, and every window is empty with first_frame = d_stream_frames[t] (a
+ * request without a stream keeps first_frame 0 and bit 2 of its flags).  Bit 2 of word 0 is
+ * reported whether or not bit 1 is.  nwindows == 0 writes a zero status, the single prefix entries
+ * and the filler; nstreams == 0 with nwindows > 0 is legal, every window then names no stream.
+ * For nwindows == nstreams and d_requests[s] = {s, d_ranges[s]}, every output is byte-identical to
+ * bnflac_select_ranges'.
+ * A negative return (nothing launched, nothing written): the null-pointer, alignment and
+ * d_sel_offsets-without-d_frame_offsets rules of bnflac_select_ranges, d_requests not 8-byte
+ * aligned, nwindows >= 2^30.
+ * No grid, loop bound or scratch size depends on nstreams or on a table's contents.  Nothing at or
+ * past position cap of the index's tables is read; nothing at or past sel_cap, nwindows (d_windows)
+ * or nwindows + 1 (the prefix tables) is written.  Asynchronous on hip_stream, no host
+ * synchronisation, on ctx's device; the only allocation is bnflac_select_ranges' scratch in ctx,
+ * which grows with nwindows (8 bytes per window) and never shrinks. */
+BNFLAC_API int bnflac_select_windows(bnflac_ctx *ctx, const uint64_t *d_frame_offsets, const bnflac_frame_info *d_info,
+                                     uint32_t cap, const uint32_t *d_stream_frames, const uint64_t *d_stream_samples,
+                                     uint32_t nstreams, const bnflac_window_request *d_requests, uint32_t nwindows,
+                                     uint64_t *d_sel_offsets, bnflac_frame_info *d_sel_info, uint32_t sel_cap,
+                                     uint32_t *d_sel_frames, uint64_t *d_sel_samples, bnflac_window *d_windows,
+                                     uint32_t *d_status, void *hip_stream);
+
+/* The same selection over tables in host memory, with the same results; no GPU needed.  0, or -1
+ * for a null argument or nwindows >= 2^30. */
+BNFLAC_API int bnflac_select_windows_host(const bnflac_frame_info *info, uint32_t cap, const uint32_t *stream_frames,
+                                          const uint64_t *stream_samples, uint32_t nstreams,
+                                          const bnflac_window_request *requests, uint32_t nwindows,
+                                          bnflac_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames,
+                                          uint64_t *sel_samples, bnflac_window *windows, uint32_t status[4]);
 
 /* The windows of a decoded selection as rows of one shape.  With stride = bnflac_out_stride(
  * out_format, sp), row s starts at d_rows + s * row_bytes: its first min(d_windows[s].nsamples,
