@@ -34,7 +34,7 @@ HIP_TUS = [
     ("bnflac_sys.hip", [], "bnflac_sys"),  # k_decode_sys
     ("bnflac_md5.hip", [], "bnflac_md5"),  # k_md5_streams (no CRC tables, no g_stats)
     ("bnflac_scan.hip", [], "bnflac_scan"),  # k_scan_streams (no CRC tables, no g_stats)
-    ("bnflac_select.hip", [], "bnflac_select"),  # k_sel_*, k_gather_ranges (no CRC tables, no g_stats)
+    ("bnflac_select.hip", [], "bnflac_select"),  # k_sel_*, k_win_*, k_shr_*, k_gather_ranges (no CRC tables, no g_stats)
     ("bnflac_f32.hip", [], "bnflac_f32"),  # k_gather_f32 (no CRC tables, no g_stats)
     ("bnflac_runtime.cpp", [], "bnflac_runtime"),
     ("bnflac_reader.cpp", [], "bnflac_reader"),

@@ -7,7 +7,9 @@
  * compiler takes it too (tools/select_ranges_sanitize.cpp builds it with the sanitizers).
  * bnflac_select_windows applies the same rule per window request, each naming its stream
  * (bnf_select_request below: k_win_select, bnflac_select_windows_host and
- * tools/select_windows_sanitize.cpp).
+ * tools/select_windows_sanitize.cpp).  bnflac_select_windows_shared takes the same requests and
+ * selects the union of their frames, each once (bnf_select_windows_shared_host below: k_shr_*,
+ * bnflac_select_windows_shared_host and tools/select_shared_sanitize.cpp).
  *
  * Stream s, T = its samples, frame i of [f0, f1) at local start L_i = out_sample_i - s0 with
  * blocksize b_i:  lo = min(first_sample, T), hi = min(lo + nsamples, T) (saturating);
@@ -23,6 +25,7 @@
 #define BNF_SELECT_H
 
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #if defined(__HIPCC__)
@@ -233,6 +236,102 @@ inline void bnf_select_windows_host(const uint64_t *offsets, const bnf_frame_inf
     status[1] = bnf_sel_sat32(nf);
     status[2] = nonempty;
     status[3] = clipped;
+}
+
+/* ---- bnflac_select_windows_shared: the requests of bnflac_select_windows, every frame selected once.
+ * Per window the rule is bnf_select_request's, unchanged.  M = the index positions some window's run
+ * [a_w, a_w + n_w) covers; in ascending position order, rank_i = the members of M below i and pos_i =
+ * the sum of their blocksizes (modulo 2^64).  Record rank_i is info[i] with out_sample = pos_i, and a
+ * window that is not empty starts at pos_{a_w} + skip_w of the shared compact PCM.  Over tables
+ * bnflac_index_streams wrote, a stream's frames tile it, so a run is contiguous in rank and in pos with
+ * the spacing out_sample had, and a window read through its record is what bnflac_select_windows'
+ * own copy yields.  M is found with a difference array over the positions: +1 at a_w, -1 at
+ * a_w + n_w (at most cap: the array has cap + 1 entries), a position is covered while the running sum
+ * is positive.  Every trip count is nwindows, cap or sel_cap. */
+
+/* The window of a request before the shared positions are known: pcm_first holds skip (0 when empty). */
+BNF_SEL_HD inline bnf_window bnf_select_shared_window(const bnf_sel_stream &o) { return bnf_select_window(o, 0); }
+
+/* The whole bnflac_select_windows_shared call on host tables: what the k_shr_* kernels compute.
+ * offsets, sel_offsets and win_sel_first may be NULL.  false: out of memory, nothing written. */
+inline bool bnf_select_windows_shared_host(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
+                                           const uint32_t *stream_frames, const uint64_t *stream_samples,
+                                           uint32_t nstreams, const bnf_window_request *requests, uint32_t nwindows,
+                                           uint64_t *sel_offsets, bnf_frame_info *sel_info, uint32_t sel_cap,
+                                           bnf_window *windows, uint32_t *win_sel_first, uint64_t totals[2],
+                                           uint32_t status[4]) {
+    bool bad = false, no_stream = false;
+    for (uint32_t w = 0; w < nwindows; w++) { /* only the slices some request names are judged */
+        const uint64_t t = requests[w].stream;
+        if (t >= nstreams)
+            no_stream = true;
+        else
+            bad = bad || !bnf_select_tables_ok(stream_frames[t], stream_frames[t + 1], stream_samples[t], stream_samples[t + 1], cap);
+    }
+    const uint32_t npos = nwindows && !bad ? cap : 0u;
+    int32_t *delta = (int32_t *)calloc((size_t)npos + 1, sizeof(int32_t)); /* the difference array, its end slot included */
+    uint32_t *rank = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)npos + 1));
+    uint64_t *pos = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)npos + 1));
+    if (!delta || !rank || !pos) {
+        free(delta);
+        free(rank);
+        free(pos);
+        return false;
+    }
+    uint32_t nonempty = 0, clipped = 0, high = 0; /* high: one past the last position a window covers */
+    for (uint32_t w = 0; w < nwindows; w++) {
+        if (bad) {
+            windows[w] = bnf_select_no_request(stream_frames, nstreams, requests[w].stream);
+            continue;
+        }
+        bnf_sel_stream o;
+        bnf_select_request(info, cap, stream_frames, stream_samples, nstreams, requests[w], o);
+        windows[w] = bnf_select_shared_window(o);
+        if (o.nframes) {
+            delta[o.first_frame] += 1;
+            delta[o.first_frame + o.nframes] -= 1;
+            if (o.first_frame + o.nframes > high) high = o.first_frame + o.nframes;
+        }
+        nonempty += (o.flags & BNF_WIN_EMPTY) ? 0u : 1u;
+        clipped += (o.flags & BNF_WIN_CLIPPED) ? 1u : 0u;
+    }
+    uint32_t nf = 0; /* at most cap */
+    uint64_t ns = 0;
+    int32_t cover = 0;
+    for (uint32_t i = 0; i < high; i++) { /* info is read at covered positions only */
+        cover += delta[i];
+        if (cover <= 0) continue;
+        rank[i] = nf;
+        pos[i] = ns;
+        if (nf < sel_cap) {
+            sel_info[nf] = info[i];
+            sel_info[nf].out_sample = ns;
+            if (sel_offsets) sel_offsets[nf] = offsets ? offsets[i] : 0;
+        }
+        nf++;
+        ns += info[i].blocksize;
+    }
+    for (uint32_t w = 0; w < nwindows; w++) {
+        const bool some = !bad && windows[w].nframes != 0;
+        if (some) windows[w].pcm_first += pos[windows[w].first_frame];
+        if (win_sel_first) win_sel_first[w] = some ? rank[windows[w].first_frame] : 0u;
+    }
+    for (uint32_t p = nf; p < sel_cap; p++) { /* filler: zeros, skipped, no error */
+        memset(&sel_info[p], 0, sizeof sel_info[p]);
+        sel_info[p].status = BNF_ST_SKIPPED;
+        sel_info[p].err = -1;
+        if (sel_offsets) sel_offsets[p] = 0;
+    }
+    totals[0] = nf;
+    totals[1] = ns;
+    status[0] = (bad ? BNF_SEL_BAD_TABLES : nf > sel_cap ? BNF_SEL_OVERFLOW : 0u) | (no_stream ? BNF_SEL_NO_STREAM : 0u);
+    status[1] = nf;
+    status[2] = nonempty;
+    status[3] = clipped;
+    free(delta);
+    free(rank);
+    free(pos);
+    return true;
 }
 
 /* The whole bnflac_select_ranges call on host tables: what the k_sel_* kernels of bnflac_select.hip

@@ -236,6 +236,19 @@ hipError_t bnf_launch_select_windows(const uint64_t *offsets, const bnf_frame_in
                                      uint32_t nwindows, uint64_t *sel_offsets, bnf_frame_info *sel_info, uint32_t sel_cap,
                                      uint32_t *sel_frames, uint64_t *sel_samples, bnf_window *windows, uint32_t *status,
                                      void *scratch, hipStream_t s);
+/* k_shr_*: the requests of k_win_* with every frame selected once (bnf_select_windows_shared_host):
+ * records and offsets by rank, windows that point into the shared compact PCM, win_sel_first (may be
+ * nullptr) the rank of each window's first frame, totals = {frames, samples}.  scratch:
+ * bnf_select_shared_scratch_bytes(cap, nwindows) bytes, 16-byte aligned: 32 bytes, 16 per position of
+ * [0, cap] and 16 per 1,024 positions, nothing per window (and 32 bytes when nwindows is 0).  Writes
+ * every status word. */
+uint64_t bnf_select_shared_scratch_bytes(uint32_t cap, uint32_t nwindows);
+hipError_t bnf_launch_select_windows_shared(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
+                                            const uint32_t *sf, const uint64_t *ss, uint32_t nstreams,
+                                            const bnf_window_request *requests, uint32_t nwindows, uint64_t *sel_offsets,
+                                            bnf_frame_info *sel_info, uint32_t sel_cap, bnf_window *windows,
+                                            uint32_t *win_sel_first, uint64_t *totals, uint32_t *status, void *scratch,
+                                            hipStream_t s);
 /* k_gather_ranges: row s = rows + s * row_bytes gets min(windows[s].nsamples, row_samples) sample
  * frames of `stride` bytes from pcm + windows[s].pcm_first * stride, then zeros up to row_samples
  * frames.  pcm 16-byte aligned, its allocation at least round_up(pcm_bytes, 16) bytes.  Zeroes

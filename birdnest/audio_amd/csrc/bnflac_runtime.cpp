@@ -637,6 +637,62 @@ extern "C" BNFLAC_API int bnflac_select_windows_host(const bnflac_frame_info *in
     return 0;
 }
 
+extern "C" BNFLAC_API int bnflac_select_windows_shared(bnflac_ctx *ctx, const uint64_t *d_frame_offsets,
+                                                       const bnflac_frame_info *d_info, uint32_t cap,
+                                                       const uint32_t *d_stream_frames, const uint64_t *d_stream_samples,
+                                                       uint32_t nstreams, const bnflac_window_request *d_requests,
+                                                       uint32_t nwindows, uint64_t *d_sel_offsets,
+                                                       bnflac_frame_info *d_sel_info, uint32_t sel_cap,
+                                                       bnflac_window *d_windows, uint32_t *d_win_sel_first,
+                                                       uint64_t *d_sel_totals, uint32_t *d_status, void *hs) {
+    if (!ctx) return fail("bnflac_select_windows_shared: null ctx");
+    DevGuard dg(ctx->device); /* launches and scratch on the context's device */
+    if (!d_status || !d_sel_totals || (sel_cap && !d_sel_info)) return fail("bnflac_select_windows_shared: null output");
+    if (nwindows && (!d_requests || !d_windows)) return fail("bnflac_select_windows_shared: null table");
+    if (nwindows && nstreams && (!d_stream_frames || !d_stream_samples))
+        return fail("bnflac_select_windows_shared: null table");
+    if (cap && nstreams && nwindows && !d_info) return fail("bnflac_select_windows_shared: null d_info");
+    if (d_sel_offsets && cap && nstreams && nwindows && !d_frame_offsets)
+        return fail("bnflac_select_windows_shared: d_sel_offsets without d_frame_offsets");
+    if ((((uintptr_t)d_info) | ((uintptr_t)d_sel_info)) & 15u)
+        return fail("bnflac_select_windows_shared: d_info and d_sel_info must be 16-byte aligned");
+    if (((uintptr_t)d_requests) & 7u) return fail("bnflac_select_windows_shared: d_requests must be 8-byte aligned");
+    if (((uintptr_t)d_sel_totals) & 7u) return fail("bnflac_select_windows_shared: d_sel_totals must be 8-byte aligned");
+    if ((((uintptr_t)d_frame_offsets) | ((uintptr_t)d_stream_samples) | ((uintptr_t)d_sel_offsets) | ((uintptr_t)d_windows)) & 7u)
+        return fail("bnflac_select_windows_shared: the 64-bit tables must be 8-byte aligned");
+    if ((((uintptr_t)d_stream_frames) | ((uintptr_t)d_win_sel_first) | ((uintptr_t)d_status)) & 3u)
+        return fail("bnflac_select_windows_shared: the 32-bit tables must be 4-byte aligned");
+    if (nwindows >= (1u << 30)) return fail("bnflac_select_windows_shared: too many windows");
+    /* the scratch of bnflac_select_ranges, which only ever grows: 16 bytes per position of the index */
+    if (!ctx->sel.grow(std::max<size_t>((size_t)bnf_select_shared_scratch_bytes(cap, nwindows), 65536)))
+        return fail("bnflac_select_windows_shared: out of device memory");
+    hipError_t e = bnf_launch_select_windows_shared(d_frame_offsets, (const bnf_frame_info *)d_info, cap, d_stream_frames,
+                                                    d_stream_samples, nstreams, (const bnf_window_request *)d_requests,
+                                                    nwindows, d_sel_offsets, (bnf_frame_info *)d_sel_info, sel_cap,
+                                                    (bnf_window *)d_windows, d_win_sel_first, d_sel_totals, d_status,
+                                                    ctx->sel.p, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_select_windows_shared: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_select_windows_shared_host(const bnflac_frame_info *info, uint32_t cap,
+                                                            const uint32_t *stream_frames, const uint64_t *stream_samples,
+                                                            uint32_t nstreams, const bnflac_window_request *requests,
+                                                            uint32_t nwindows, bnflac_frame_info *sel_info, uint32_t sel_cap,
+                                                            bnflac_window *windows, uint32_t *win_sel_first,
+                                                            uint64_t sel_totals[2], uint32_t status[4]) {
+    if (!status || !sel_totals || (sel_cap && !sel_info)) return fail("bnflac_select_windows_shared_host: null output");
+    if (nwindows && (!requests || !windows)) return fail("bnflac_select_windows_shared_host: null table");
+    if (nwindows && nstreams && (!stream_frames || !stream_samples))
+        return fail("bnflac_select_windows_shared_host: null table");
+    if (cap && nstreams && nwindows && !info) return fail("bnflac_select_windows_shared_host: null info");
+    if (nwindows >= (1u << 30)) return fail("bnflac_select_windows_shared_host: too many windows");
+    if (!bnf_select_windows_shared_host(nullptr, (const bnf_frame_info *)info, cap, stream_frames, stream_samples, nstreams,
+                                        (const bnf_window_request *)requests, nwindows, nullptr, (bnf_frame_info *)sel_info,
+                                        sel_cap, (bnf_window *)windows, win_sel_first, sel_totals, status))
+        return fail("bnflac_select_windows_shared_host: out of memory");
+    return 0;
+}
+
 extern "C" BNFLAC_API int bnflac_gather_ranges(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
                                                const bnflac_stream_params *sp, const bnflac_window *d_windows,
                                                uint32_t nstreams, uint32_t row_samples, uint64_t row_bytes, uint8_t *d_rows,

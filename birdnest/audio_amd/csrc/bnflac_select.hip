@@ -1,8 +1,8 @@
 /*
  * bnflac_select.hip -- sample windows of a batch: k_sel_streams / k_sel_scan / k_sel_apply /
- * k_sel_emit (bnflac_select_ranges) and k_win_select / k_win_scan / k_win_apply
- * (bnflac_select_windows) cut the index of bnflac_index_streams down to the frames the
- * windows need, k_gather_ranges (bnflac_gather_ranges) copies the decoded windows into rows of
+ * k_sel_emit (bnflac_select_ranges), k_win_select / k_win_scan / k_win_apply
+ * (bnflac_select_windows) and k_shr_* (bnflac_select_windows_shared) cut the index of
+ * bnflac_index_streams down to the frames the windows need, k_gather_ranges (bnflac_gather_ranges) copies the decoded windows into rows of
  * one shape.  No CRC tables, no g_stats, no ablate word.
  *
  * Selection.  The rule is bnf_select.h's.  Four launches, and launch boundaries are the only
@@ -30,6 +30,27 @@
  * scanned in 64 bits: k_win_select leaves each window's prefix inside its workgroup in the scratch,
  * k_win_apply adds the workgroup's base and writes min(prefix, UINT32_MAX).  The emit compares a
  * position below sel_cap with prefix entries only, and a saturated entry is above every position.
+ *
+ * Shared selection (bnflac_select_windows_shared): the same requests, every frame selected once.  A
+ * mark / scan / compact over the index positions [0, cap), launch boundaries again the only ordering:
+ *   k_shr_mark     one lane per window: bnf_select_request, the window record with pcm_first = skip,
+ *                  +1 / -1 into a difference array delta[cap + 1] (integer atomics), the ballots of
+ *                  k_win_select and the highest position any run ends at (atomicMax).
+ *   k_shr_cover    1,024 positions per workgroup: the running sum of delta inside the workgroup, in
+ *                  place, and the workgroup's sum.
+ *   k_shr_scan<0>  one workgroup: the exclusive scan of those sums.
+ *   k_shr_rank     covered = base + running sum > 0; the workgroup's exclusive scan of (covered,
+ *                  covered ? blocksize : 0) to rank / pos, the sums per workgroup.  d_info is read at
+ *                  covered positions only.
+ *   k_shr_scan<1>  one workgroup: the exclusive scan of those sums, the totals and the status words.
+ *   k_shr_emit     8 lanes per position, as k_sel_emit: a covered position copies its record to its
+ *                  rank (below sel_cap) with out_sample = pos; output positions at or past the total
+ *                  get the filler.
+ *   k_shr_windows  one lane per window: pcm_first += pos of its first frame, win_sel_first = its rank;
+ *                  under the bad flag the emptied records.
+ * Grids and loop bounds are cap, nwindows and sel_cap.  A position workgroup at or past the highest
+ * marked position (clamped to cap) writes zero sums and leaves.  Scratch: 32 bytes, 16 per position
+ * (delta 4, rank 4, pos 8) and 16 per 1,024 positions; nothing per window.
  *
  * Gather.  Row s = min(nsamples, row_samples) sample frames from pcm_first, then zeros up to
  * row_samples.  Source offset (pcm_first * stride) and destination offset (s * row_bytes) have
@@ -390,6 +411,276 @@ extern "C" hipError_t bnf_launch_select_windows(const uint64_t *offsets, const b
         hipLaunchKernelGGL(k_sel_emit, dim3((uint32_t)((threads + EMIT_THREADS - 1) / EMIT_THREADS)), dim3(EMIT_THREADS), 0, s,
                            offsets, info, cap, sel_frames, sel_samples, nwindows, windows, sel_offsets, sel_info, sel_cap);
     }
+    return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ shared selection: every frame once
+ * ctl: [0] bad flag, [1] windows that are not empty, [2] windows clipped, [3] a request names no stream,
+ * [4] one past the last position a window covers (never above cap), [5] frames selected, 0 under the
+ * bad flag (written by the final k_shr_scan for the emit), [6], [7] unused. */
+#define SHR_CTL_WORDS 8
+
+__global__ __launch_bounds__(SEL_BLOCK) void k_shr_mark(const bnf_frame_info *__restrict__ info, uint32_t cap,
+                                                        const uint32_t *__restrict__ sf, const uint64_t *__restrict__ ss,
+                                                        uint32_t nstreams, const bnf_window_request *__restrict__ requests,
+                                                        uint32_t nwindows, bnf_window *__restrict__ windows,
+                                                        uint32_t *__restrict__ ctl, int32_t *__restrict__ delta) {
+    const uint32_t w = blockIdx.x * SEL_BLOCK + threadIdx.x;
+    const bool live = w < nwindows;
+    bnf_sel_stream o;
+    o.nsamples = o.hull = 0;
+    o.skip = o.first_frame = o.nframes = 0;
+    o.flags = BNF_WIN_EMPTY;
+    uint32_t verdict = BNF_REQ_OK;
+    if (live) {
+        verdict = bnf_select_request(info, cap, sf, ss, nstreams, requests[w], o);
+        windows[w] = bnf_select_shared_window(o);
+    }
+    uint32_t end = 0; /* a run lies inside its stream's slice: first_frame + nframes <= cap, delta has cap + 1 entries */
+    if (o.nframes) {
+        end = o.first_frame + o.nframes;
+        atomicAdd(&delta[o.first_frame], 1);
+        atomicAdd(&delta[end], -1);
+    }
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const uint32_t other = __shfl_xor(end, d);
+        end = other > end ? other : end;
+    }
+    const bool any_bad = __ballot(verdict == BNF_REQ_BAD_SLICE) != 0;
+    const bool any_none = __ballot(verdict == BNF_REQ_NO_STREAM) != 0;
+    const uint32_t nonempty = (uint32_t)__popcll(__ballot(live && !(o.flags & BNF_WIN_EMPTY)));
+    const uint32_t clipped = (uint32_t)__popcll(__ballot(live && (o.flags & BNF_WIN_CLIPPED)));
+    if ((threadIdx.x & 63u) == 0) {
+        if (any_bad) atomicOr(&ctl[0], 1u);
+        if (nonempty) atomicAdd(&ctl[1], nonempty);
+        if (clipped) atomicAdd(&ctl[2], clipped);
+        if (any_none) atomicOr(&ctl[3], 1u);
+        if (end) atomicMax(&ctl[4], end);
+    }
+}
+
+/* The running sum of delta inside each workgroup's 1,024 positions, in place, and the workgroup's sum.
+ * A workgroup at or past ctl[4] holds zeros only: it writes a zero sum and leaves. */
+__global__ __launch_bounds__(SEL_BLOCK) void k_shr_cover(int32_t *__restrict__ delta, uint32_t cap,
+                                                         const uint32_t *__restrict__ ctl, uint32_t *__restrict__ wg_cover) {
+    const uint32_t high = ctl[4] < cap ? ctl[4] : cap;
+    if (blockIdx.x * SEL_BLOCK >= high) {
+        if (threadIdx.x == 0) wg_cover[blockIdx.x] = 0;
+        return;
+    }
+    const uint32_t i = blockIdx.x * SEL_BLOCK + threadIdx.x;
+    const uint32_t d = i < cap ? (uint32_t)delta[i] : 0u; /* sums modulo 2^32 are the signed sums */
+    uint32_t ef, tf;
+    uint64_t es, ts;
+    sel_block_scan<uint32_t>(d, 0, ef, es, tf, ts);
+    if (i < cap) delta[i] = (int32_t)(ef + d);
+    if (threadIdx.x == 0) wg_cover[blockIdx.x] = tf;
+}
+
+/* One workgroup: the workgroup sums become their exclusive prefixes.  LAST: frames and samples of the
+ * covered positions, then the totals and the status words; else the cover sums alone. */
+template <bool LAST>
+__global__ __launch_bounds__(SEL_BLOCK) void k_shr_scan(uint32_t *__restrict__ wg_frames, uint64_t *__restrict__ wg_samples,
+                                                        uint32_t nwg, uint32_t sel_cap, uint32_t *__restrict__ ctl,
+                                                        uint64_t *__restrict__ totals, uint32_t *__restrict__ status) {
+    uint32_t carry_f = 0;
+    uint64_t carry_s = 0;
+    for (uint32_t base = 0; base < nwg; base += SEL_BLOCK) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t f = i < nwg ? wg_frames[i] : 0u;
+        const uint64_t s = LAST && i < nwg ? wg_samples[i] : 0u;
+        uint32_t ef, tf;
+        uint64_t es, ts;
+        sel_block_scan<uint32_t>(f, s, ef, es, tf, ts);
+        if (i < nwg) {
+            wg_frames[i] = carry_f + ef;
+            if (LAST) wg_samples[i] = carry_s + es;
+        }
+        carry_f += tf;
+        carry_s += ts;
+    }
+    if (LAST && threadIdx.x == 0) {
+        const bool bad = ctl[0] != 0;
+        const uint32_t none = ctl[3] ? BNF_SEL_NO_STREAM : 0u;
+        ctl[5] = bad ? 0u : carry_f;
+        totals[0] = bad ? 0u : carry_f;
+        totals[1] = bad ? 0u : carry_s;
+        status[0] = (bad ? BNF_SEL_BAD_TABLES : carry_f > sel_cap ? BNF_SEL_OVERFLOW : 0u) | none;
+        status[1] = bad ? 0u : carry_f;
+        status[2] = bad ? 0u : ctl[1];
+        status[3] = bad ? 0u : ctl[2];
+    }
+}
+
+/* Position i is covered when its workgroup's base plus its running sum is positive.  The exclusive scan
+ * of (covered, covered ? blocksize : 0) inside the workgroup goes to rank / pos, covered itself replaces
+ * the running sum in delta.  info is read at covered positions only. */
+__global__ __launch_bounds__(SEL_BLOCK) void k_shr_rank(const bnf_frame_info *__restrict__ info, uint32_t cap,
+                                                        const uint32_t *__restrict__ ctl, const uint32_t *__restrict__ wg_cover,
+                                                        int32_t *__restrict__ delta, uint32_t *__restrict__ rank,
+                                                        uint64_t *__restrict__ pos, uint32_t *__restrict__ wg_frames,
+                                                        uint64_t *__restrict__ wg_samples) {
+    const uint32_t high = ctl[4] < cap ? ctl[4] : cap;
+    if (blockIdx.x * SEL_BLOCK >= high) {
+        if (threadIdx.x == 0) {
+            wg_frames[blockIdx.x] = 0;
+            wg_samples[blockIdx.x] = 0;
+        }
+        return;
+    }
+    const uint32_t i = blockIdx.x * SEL_BLOCK + threadIdx.x;
+    const bool covered = i < cap && (int32_t)(wg_cover[blockIdx.x] + (uint32_t)delta[i]) > 0;
+    const uint32_t bs = covered ? info[i].blocksize : 0u;
+    uint32_t ef, tf;
+    uint64_t es, ts;
+    sel_block_scan<uint32_t>(covered ? 1u : 0u, bs, ef, es, tf, ts);
+    if (i < cap) {
+        delta[i] = covered ? 1 : 0;
+        rank[i] = ef;
+        pos[i] = es;
+    }
+    if (threadIdx.x == 0) {
+        wg_frames[blockIdx.x] = tf;
+        wg_samples[blockIdx.x] = ts;
+    }
+}
+
+/* 8 lanes per position q, as in k_sel_emit.  As an index position (q below ctl[4]): a covered one copies
+ * its record to its rank, if that is below sel_cap, with out_sample = its pos.  As a position of the
+ * output (q below sel_cap): at or past the frame total it gets the filler.  The two sets of output
+ * positions are disjoint (rank < total <= filler). */
+__global__ __launch_bounds__(EMIT_THREADS) void k_shr_emit(const uint64_t *__restrict__ offsets,
+                                                           const bnf_frame_info *__restrict__ info, uint32_t cap,
+                                                           const uint32_t *__restrict__ ctl, const int32_t *__restrict__ delta,
+                                                           const uint32_t *__restrict__ rank, const uint64_t *__restrict__ pos,
+                                                           const uint32_t *__restrict__ wg_frames,
+                                                           const uint64_t *__restrict__ wg_samples,
+                                                           uint64_t *__restrict__ sel_offsets,
+                                                           bnf_frame_info *__restrict__ sel_info, uint32_t sel_cap) {
+    const uint64_t gid = (uint64_t)blockIdx.x * EMIT_THREADS + threadIdx.x;
+    const uint64_t q64 = gid >> 3;
+    const uint32_t part = (uint32_t)gid & 7u; /* bytes [16 part, 16 part + 16) of the record */
+    const uint32_t high = ctl[0] ? 0u : ctl[4] < cap ? ctl[4] : cap;
+    if (q64 >= high && q64 >= sel_cap) return;
+    const uint32_t q = (uint32_t)q64;
+    if (q < sel_cap && q >= ctl[5]) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u); /* the filler: zeros, status 3 (skipped), err -1 */
+        if (part == 0) {
+            v.x = BNF_ST_SKIPPED;
+            v.y = 0xffffffffu;
+        }
+        ((uint4 *)(sel_info + q))[part] = v;
+        if (part == 0 && sel_offsets) sel_offsets[q] = 0;
+    }
+    if (q < high && delta[q]) {
+        const uint32_t r = wg_frames[q / SEL_BLOCK] + rank[q];
+        if (r < sel_cap) {
+            uint4 v = ((const uint4 *)(info + q))[part];
+            if (part == 4) { /* out_sample: bytes 64..71 */
+                const uint64_t os = wg_samples[q / SEL_BLOCK] + pos[q];
+                v.x = (uint32_t)os;
+                v.y = (uint32_t)(os >> 32);
+            }
+            ((uint4 *)(sel_info + r))[part] = v;
+            if (part == 0 && sel_offsets) sel_offsets[r] = offsets ? offsets[q] : 0u;
+        }
+    }
+}
+
+/* One lane per window: pcm_first gains the pos of the window's first frame, win_sel_first its rank; under
+ * the bad flag every window is emptied. */
+__global__ __launch_bounds__(SEL_BLOCK) void k_shr_windows(const uint32_t *__restrict__ sf, uint32_t nstreams,
+                                                           const bnf_window_request *__restrict__ requests, uint32_t nwindows,
+                                                           uint32_t cap, const uint32_t *__restrict__ ctl,
+                                                           const uint32_t *__restrict__ rank, const uint64_t *__restrict__ pos,
+                                                           const uint32_t *__restrict__ wg_frames,
+                                                           const uint64_t *__restrict__ wg_samples,
+                                                           bnf_window *__restrict__ windows, uint32_t *__restrict__ win_sel_first) {
+    const uint32_t w = blockIdx.x * SEL_BLOCK + threadIdx.x;
+    if (w >= nwindows) return;
+    uint32_t first = 0;
+    if (ctl[0]) {
+        windows[w] = bnf_select_no_request(sf, nstreams, requests[w].stream);
+    } else {
+        const uint32_t a = windows[w].first_frame;
+        if (windows[w].nframes && a < cap) { /* a < cap holds for every run k_shr_mark wrote */
+            windows[w].pcm_first += wg_samples[a / SEL_BLOCK] + pos[a];
+            first = wg_frames[a / SEL_BLOCK] + rank[a];
+        }
+    }
+    if (win_sel_first) win_sel_first[w] = first;
+}
+
+/* Scratch: 32 bytes of ctl, then 16 bytes per position (delta 4, rank 4, pos 8; delta has one entry more)
+ * and 16 bytes per 1,024 positions (the three workgroup sums), each table rounded up to 16 bytes.
+ * Nothing per window: the window records are written in place.  npos = cap, or 0 without windows. */
+struct shr_scratch {
+    uint32_t *ctl;
+    int32_t *delta;
+    uint32_t *rank, *wg_cover, *wg_frames;
+    uint64_t *pos, *wg_samples;
+    uint64_t bytes;
+};
+
+static shr_scratch shr_layout(void *scratch, uint32_t npos) {
+    const uint64_t nwg = ((uint64_t)npos + SEL_BLOCK - 1) / SEL_BLOCK;
+    auto up16 = [](uint64_t n) { return (n + 15u) & ~(uint64_t)15; };
+    uint8_t *p = (uint8_t *)scratch;
+    shr_scratch x;
+    x.ctl = (uint32_t *)p; /* ctl and delta are zeroed by one memset */
+    x.delta = (int32_t *)(p + 4u * SHR_CTL_WORDS);
+    p += up16(4u * SHR_CTL_WORDS + 4u * ((uint64_t)npos + 1));
+    x.pos = (uint64_t *)p;
+    p += up16(8u * (uint64_t)npos);
+    x.wg_samples = (uint64_t *)p;
+    p += up16(8u * nwg);
+    x.rank = (uint32_t *)p;
+    p += up16(4u * (uint64_t)npos);
+    x.wg_cover = (uint32_t *)p;
+    p += up16(4u * nwg);
+    x.wg_frames = (uint32_t *)p;
+    p += up16(4u * nwg);
+    x.bytes = (uint64_t)(p - (uint8_t *)scratch);
+    return x;
+}
+
+extern "C" uint64_t bnf_select_shared_scratch_bytes(uint32_t cap, uint32_t nwindows) {
+    return shr_layout(nullptr, nwindows ? cap : 0u).bytes;
+}
+
+extern "C" hipError_t bnf_launch_select_windows_shared(const uint64_t *offsets, const bnf_frame_info *info, uint32_t cap,
+                                                       const uint32_t *sf, const uint64_t *ss, uint32_t nstreams,
+                                                       const bnf_window_request *requests, uint32_t nwindows,
+                                                       uint64_t *sel_offsets, bnf_frame_info *sel_info, uint32_t sel_cap,
+                                                       bnf_window *windows, uint32_t *win_sel_first, uint64_t *totals,
+                                                       uint32_t *status, void *scratch, hipStream_t s) {
+    const uint32_t npos = nwindows ? cap : 0u; /* without windows no position is looked at */
+    const uint32_t nwg = (uint32_t)(((uint64_t)nwindows + SEL_BLOCK - 1) / SEL_BLOCK);
+    const uint32_t npwg = (uint32_t)(((uint64_t)npos + SEL_BLOCK - 1) / SEL_BLOCK);
+    const shr_scratch x = shr_layout(scratch, npos);
+    hipError_t e = hipMemsetAsync(x.ctl, 0, 4u * SHR_CTL_WORDS + 4u * ((size_t)npos + 1), s);
+    if (e != hipSuccess) return e;
+    if (nwg)
+        hipLaunchKernelGGL(k_shr_mark, dim3(nwg), dim3(SEL_BLOCK), 0, s, info, cap, sf, ss, nstreams, requests, nwindows, windows,
+                           x.ctl, x.delta);
+    if (npwg) {
+        hipLaunchKernelGGL(k_shr_cover, dim3(npwg), dim3(SEL_BLOCK), 0, s, x.delta, cap, x.ctl, x.wg_cover);
+        hipLaunchKernelGGL(k_shr_scan<false>, dim3(1), dim3(SEL_BLOCK), 0, s, x.wg_cover, (uint64_t *)nullptr, npwg, sel_cap,
+                           x.ctl, (uint64_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(k_shr_rank, dim3(npwg), dim3(SEL_BLOCK), 0, s, info, cap, x.ctl, x.wg_cover, x.delta, x.rank, x.pos,
+                           x.wg_frames, x.wg_samples);
+    }
+    hipLaunchKernelGGL(k_shr_scan<true>, dim3(1), dim3(SEL_BLOCK), 0, s, x.wg_frames, x.wg_samples, npwg, sel_cap, x.ctl, totals,
+                       status);
+    const uint64_t threads = 8ull * (npos > sel_cap ? npos : sel_cap);
+    if (threads)
+        hipLaunchKernelGGL(k_shr_emit, dim3((uint32_t)((threads + EMIT_THREADS - 1) / EMIT_THREADS)), dim3(EMIT_THREADS), 0, s,
+                           offsets, info, cap, x.ctl, x.delta, x.rank, x.pos, x.wg_frames, x.wg_samples, sel_offsets, sel_info,
+                           sel_cap);
+    if (nwg)
+        hipLaunchKernelGGL(k_shr_windows, dim3(nwg), dim3(SEL_BLOCK), 0, s, sf, nstreams, requests, nwindows, cap, x.ctl, x.rank,
+                           x.pos, x.wg_frames, x.wg_samples, windows, win_sel_first);
     return hipGetLastError();
 }
 

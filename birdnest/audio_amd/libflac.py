@@ -130,6 +130,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_scan_streams", "bnflac_scan_stream_host",
                  "bnflac_select_ranges", "bnflac_select_ranges_host", "bnflac_gather_ranges",
                  "bnflac_select_windows", "bnflac_select_windows_host",
+                 "bnflac_select_windows_shared", "bnflac_select_windows_shared_host",
                  "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
@@ -234,6 +235,12 @@ def load() -> ctypes.CDLL:
     L.bnflac_select_windows_host.restype = i
     L.bnflac_select_windows_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, ctypes.c_uint32, p,
                                              ctypes.c_uint32, p, p, p, p]
+    L.bnflac_select_windows_shared.restype = i
+    L.bnflac_select_windows_shared.argtypes = [p, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, ctypes.c_uint32, p, p,
+                                               ctypes.c_uint32, p, p, p, p, p]
+    L.bnflac_select_windows_shared_host.restype = i
+    L.bnflac_select_windows_shared_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, ctypes.c_uint32, p,
+                                                    ctypes.c_uint32, p, p, p, p]
     L.bnflac_gather_ranges.restype = i
     L.bnflac_gather_ranges.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                        p, p, p]
@@ -505,6 +512,31 @@ def select_windows_host(info: np.ndarray, cap: int, stream_frames, stream_sample
     if rc != 0:
         raise RuntimeError(load().bnflac_last_error().decode())
     return sel, sel_f, sel_s, win, status
+
+
+def select_windows_shared_host(info: np.ndarray, cap: int, stream_frames, stream_samples, requests, sel_cap: int):
+    """select_windows_shared over host tables (bnflac_select_windows_shared_host, no GPU): the
+    requests of select_windows_host, every frame they need selected once.
+    -> (sel_info[sel_cap], windows[k], win_sel_first uint32[k], totals uint64[2] = (frames, samples),
+        status uint32[4]) for k requests, the windows in their order."""
+    info = np.ascontiguousarray(info, dtype=FRAME_INFO_DTYPE)
+    sf = np.ascontiguousarray(stream_frames, dtype=np.uint32)
+    ss = np.ascontiguousarray(stream_samples, dtype=np.uint64)
+    n = len(sf) - 1
+    if n < 0 or len(ss) != n + 1 or len(info) < min(cap, int(sf.max(initial=0))):
+        raise ValueError("stream_frames and stream_samples hold nstreams + 1 entries, info the records below cap")
+    r = requests if isinstance(requests, np.ndarray) and requests.dtype == WINDOW_REQUEST_DTYPE else window_requests(requests)
+    r = np.ascontiguousarray(r)
+    k = len(r)
+    sel = np.zeros(sel_cap, dtype=FRAME_INFO_DTYPE)
+    win, first = np.zeros(k, dtype=WINDOW_DTYPE), np.zeros(k, np.uint32)
+    totals, status = np.zeros(2, np.uint64), np.zeros(4, np.uint32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    rc = load().bnflac_select_windows_shared_host(vp(info), cap, vp(sf), vp(ss), n, vp(r), k, vp(sel), sel_cap, vp(win),
+                                                  vp(first), vp(totals), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return sel, win, first, totals, status
 
 
 def stream_table(streams, nbytes: int) -> np.ndarray:
@@ -878,6 +910,46 @@ class BatchDecoder:
             raise RuntimeError(self.L.bnflac_last_error().decode())
         return d_sel_offs, d_sel_info, d_sel_f, d_sel_s, d_win, d_status
 
+    def select_windows_shared(self, d_offsets, d_info, cap: int, d_stream_frames, d_stream_samples, nstreams: int,
+                              requests, sel_cap: int, stream=None):
+        """select_windows for crops that overlap (bnflac_select_windows_shared): the union of the
+        frames the requests need, each selected once, and windows that point into the one compact
+        PCM those frames decode into.  Arguments as for select_windows; the scratch kept in the
+        context grows by 16 bytes per position of cap.
+        -> (d_sel_offsets int64[sel_cap], d_sel_info uint8[sel_cap*128] ready for
+            decode_parsed(nframes=sel_cap), d_windows uint8[k*32] for gather_ranges(nstreams=k),
+            d_win_sel_first int32[k], d_totals int64[2] = (frames, samples), d_status int32[4]) for k
+        requests, all on the device and not synchronised."""
+        import torch
+        dev = d_info.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        on_device = isinstance(requests, torch.Tensor)
+        if on_device:
+            if not requests.is_cuda or requests.element_size() != 8 or requests.numel() % 3 or not requests.is_contiguous():
+                raise ValueError("device requests are a contiguous CUDA tensor of 3 64-bit words per window")
+            d_req, k = requests, requests.numel() // 3
+        else:
+            table = window_requests(requests)
+            k = len(table)
+        with torch.cuda.stream(s):
+            if not on_device:
+                d_req = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev) if k else None
+            d_sel_offs = torch.zeros(max(sel_cap, 1), dtype=torch.int64, device=dev)
+            d_sel_info = torch.zeros(max(sel_cap, 1) * FRAME_INFO_BYTES, dtype=torch.uint8, device=dev)
+            d_win = torch.zeros(max(k, 1) * WINDOW_BYTES, dtype=torch.uint8, device=dev)
+            d_first = torch.zeros(max(k, 1), dtype=torch.int32, device=dev)
+            d_totals = torch.zeros(2, dtype=torch.int64, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self.L.bnflac_select_windows_shared(self.ctx, vp(d_offsets), vp(d_info), cap, vp(d_stream_frames),
+                                                 vp(d_stream_samples), nstreams, vp(d_req) if k else None, k,
+                                                 vp(d_sel_offs) if d_offsets is not None else None, vp(d_sel_info),
+                                                 sel_cap, vp(d_win), vp(d_first), vp(d_totals), vp(d_status),
+                                                 self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_sel_offs, d_sel_info, d_win, d_first[:k], d_totals, d_status
+
     def gather_ranges(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, row_samples: int,
                       row_bytes: Optional[int] = None, d_rows=None, stream=None, pcm_bytes=None):
         """The windows of a decoded selection as rows of one shape (bnflac_gather_ranges): row s is
@@ -1038,10 +1110,13 @@ class BatchDecoder:
                                                                      stream=s)
         return Corpus(d_bytes, nbytes, sp, n, cap, d_offs, d_info, d_sf, d_ss, st_scan, st_index)
 
-    def _decode_crop_selection(self, corpus: Corpus, requests, nsamples, fmt, s):
+    def _decode_crop_selection(self, corpus: Corpus, requests, nsamples, fmt, s, shared=False, max_frames=None,
+                               max_samples=None):
         """The front of decode_crops and decode_crops_f32: select_windows over the corpus's index ->
         decode_parsed(nframes = sel_cap) of the copied records into a compact PCM in fmt, on stream s.
-        -> (d_pcm, d_windows, nwindows, {"select" -> int32[4]})"""
+        shared: select_windows_shared in select_windows' place, with sel_cap = max_frames and a PCM of
+        max_samples sample frames where they are given, and "totals" in the status.
+        -> (d_pcm, d_windows, nwindows, the PCM's bytes when shared else None, {"select" -> int32[4]})"""
         import torch
         sp = corpus.sp
         if nsamples < 1:
@@ -1056,17 +1131,31 @@ class BatchDecoder:
             requests = [(r[0], r[1], nsamples) if len(r) == 2 else tuple(r) for r in requests]
             k = len(requests)
         sel_cap = k * ((nsamples - 1) // sp.min_blocksize + 2)
+        pcm_samples = k * (nsamples + 2 * (sp.max_blocksize - 1))
         stride = out_stride(fmt, sp)
-        _, d_sel_info, _, _, d_win, st_select = self.select_windows(corpus.d_offsets, corpus.d_info, corpus.cap,
-                                                                    corpus.d_stream_frames, corpus.d_stream_samples,
-                                                                    corpus.nstreams, requests, sel_cap, stream=s)
+        status = {}
+        if shared:  # the union is never larger than the sum, nor than the index
+            sel_cap = min(sel_cap, corpus.cap) if max_frames is None else max_frames
+            pcm_samples = pcm_samples if max_samples is None else max_samples
+            if sel_cap < 0 or pcm_samples < 0:
+                raise ValueError("max_frames and max_samples are counts")
+            _, d_sel_info, d_win, _, status["totals"], status["select"] = self.select_windows_shared(
+                corpus.d_offsets, corpus.d_info, corpus.cap, corpus.d_stream_frames, corpus.d_stream_samples,
+                corpus.nstreams, requests, sel_cap, stream=s)
+        else:
+            if max_frames is not None or max_samples is not None:
+                raise ValueError("max_frames and max_samples size the shared selection: pass shared=True")
+            _, d_sel_info, _, _, d_win, status["select"] = self.select_windows(
+                corpus.d_offsets, corpus.d_info, corpus.cap, corpus.d_stream_frames, corpus.d_stream_samples,
+                corpus.nstreams, requests, sel_cap, stream=s)
         with torch.cuda.stream(s):
-            pcm_bytes = k * (nsamples + 2 * (sp.max_blocksize - 1)) * stride
+            pcm_bytes = pcm_samples * stride
             d_pcm = torch.zeros(max((pcm_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=corpus.d_bytes.device)
         self.decode_parsed(corpus.d_bytes, corpus.nbytes, sel_cap, sp, fmt, d_pcm, d_sel_info, stream=s)
-        return d_pcm, d_win, k, {"select": st_select}
+        return d_pcm, d_win, k, pcm_bytes if shared else None, status
 
-    def decode_crops(self, corpus: Corpus, requests, nsamples: int, fmt: int, stream=None):
+    def decode_crops(self, corpus: Corpus, requests, nsamples: int, fmt: int, stream=None, shared: bool = False,
+                     max_frames: Optional[int] = None, max_samples: Optional[int] = None):
         """Any crops of nsamples sample frames out of an indexed corpus, as rows in request order:
         select_windows -> decode_parsed(nframes = sel_cap) -> gather_ranges over the index that
         index_corpus made, with no host synchronisation and nothing read back.
@@ -1078,14 +1167,22 @@ class BatchDecoder:
         k * (nsamples + 2 * (max_blocksize - 1)) sample frames.  The decode completes the copied
         records, never the corpus's, so one corpus serves any number of calls; each must be ordered
         after index_corpus (the same stream, or the caller's events).
+        shared: select_windows_shared in select_windows' place, for crops that overlap (sliding
+        windows): every frame is selected and decoded once and the rows are the same.  max_frames,
+        max_samples (shared only): the records and the sample frames of the compact PCM to provide,
+        where the caller knows the union's size; the defaults are the bounds above with sel_cap no
+        larger than corpus.cap, which always suffice.  Too small a max_frames shows as bit 0 of the
+        select status, a crop whose samples were not provided as a zero row and the gather status.
         -> (rows, status): rows int32[k, nsamples, channels] for OUT_INTERLEAVED32, else
-        uint8[k, nsamples * stride]; status: {"select", "gather"} -> device int32[4]."""
+        uint8[k, nsamples * stride]; status: {"select", "gather"} -> device int32[4], and with
+        shared "totals" -> device int64[2], the frames and sample frames selected."""
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()
         sp = corpus.sp
-        d_pcm, d_win, k, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s)
+        d_pcm, d_win, k, pcm_bytes, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s, shared,
+                                                                         max_frames, max_samples)
         stride = out_stride(fmt, sp)
-        d_rows, status["gather"] = self.gather_ranges(d_pcm, fmt, sp, d_win, k, nsamples, stream=s)
+        d_rows, status["gather"] = self.gather_ranges(d_pcm, fmt, sp, d_win, k, nsamples, stream=s, pcm_bytes=pcm_bytes)
         with torch.cuda.stream(s):
             if fmt == OUT_INTERLEAVED32:
                 rows = d_rows[: k * nsamples * stride].view(torch.int32).view(k, nsamples, sp.channels)
@@ -1094,9 +1191,11 @@ class BatchDecoder:
         return rows, status
 
     def decode_crops_f32(self, corpus: Corpus, requests, nsamples: int, fmt: Optional[int] = None, mono: bool = False,
-                         stream=None):
+                         stream=None, shared: bool = False, max_frames: Optional[int] = None,
+                         max_samples: Optional[int] = None):
         """decode_crops with gather_ranges_f32 as its last step: the crops as float32 channel planes
-        in [-1, 1), in request order.  fmt, mono: as for decode_windows_f32.
+        in [-1, 1), in request order.  fmt, mono: as for decode_windows_f32; shared, max_frames,
+        max_samples: as for decode_crops.
         -> (float32[k, planes, nsamples], status)"""
         import torch
         sp = corpus.sp
@@ -1104,8 +1203,10 @@ class BatchDecoder:
         if not md5_layout(fmt, sp):
             raise ValueError("the layout's bytes are not the samples: gather_ranges_f32 cannot read it")
         s = stream if stream is not None else torch.cuda.current_stream()
-        d_pcm, d_win, k, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s)
-        planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, k, nsamples, mono=mono, stream=s)
+        d_pcm, d_win, k, pcm_bytes, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s, shared,
+                                                                         max_frames, max_samples)
+        planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, k, nsamples, mono=mono, stream=s,
+                                                          pcm_bytes=pcm_bytes)
         return planes, status
 
     def crc_handoff(self, nframes: int) -> np.ndarray:

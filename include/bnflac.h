@@ -19,6 +19,8 @@
  * bnflac_gather_ranges_f32 where the windows are wanted as float32 channel planes in [-1, 1).
  * For any crops of a batch that stays resident (several of one stream, none of most, in the
  * sampler's order), bnflac_select_windows takes bnflac_select_ranges' place over an index made once.
+ * Where the crops overlap (sliding windows over whole recordings), bnflac_select_windows_shared takes
+ * the same requests and selects every frame once, the windows pointing into one shared compact PCM.
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -495,6 +497,69 @@ BNFLAC_API int bnflac_select_windows_host(const bnflac_frame_info *info, uint32_
                                           const bnflac_window_request *requests, uint32_t nwindows,
                                           bnflac_frame_info *sel_info, uint32_t sel_cap, uint32_t *sel_frames,
                                           uint64_t *sel_samples, bnflac_window *windows, uint32_t status[4]);
+
+/* bnflac_select_windows for windows that overlap: the union of the frames the windows need, each
+ * selected, copied and decoded once, and window records that point into that shared compact PCM.
+ * With a window W and a hop H < W over a stream, bnflac_select_windows selects every frame about
+ * W / H times; this call selects it once.  The inputs are bnflac_select_windows', and so is the rule
+ * per window w: its run [a_w, a_w + n_w) of index positions, skip_w, nsamples_w and flags_w (no
+ * stream, clipping, "a frame that only touches is not selected"), and unusable slices are judged only
+ * where a request names them.  The chain is bnflac_select_windows_shared ->
+ * bnflac_decode_parsed(nframes = sel_cap) -> bnflac_gather_ranges / bnflac_gather_ranges_f32 with
+ * nstreams = nwindows; the gathers take any window table, and two windows may read the same PCM.
+ * If some named slice is unusable, the outcome is bnflac_select_windows': nothing is selected, every
+ * window is empty with first_frame = d_stream_frames[t] (0 and flags bit 2 without a stream), every
+ * record below sel_cap is filler, the totals and status words 1-3 are 0, bit 1 of word 0 is set and
+ * bit 2 is still reported.
+ * Otherwise let M be the index positions in the union over w of [a_w, a_w + n_w), and for i in M, in
+ * ascending position order, rank_i = the members of M below i, pos_i = the sum of their blocksizes
+ * (modulo 2^64), F = |M| and S = the sum of the blocksizes over M.
+ *   d_sel_info[rank_i]: d_info[i] byte for byte apart from out_sample = pos_i, written only where
+ *     rank_i < sel_cap; d_sel_offsets[rank_i] (may be NULL) = d_frame_offsets[i].  Positions
+ *     [F, sel_cap) are the filler records of bnflac_select_ranges, d_sel_offsets 0.
+ *   d_windows[w] (nwindows records): for a window that is not empty pcm_first = pos_{a_w} + skip_w;
+ *     nsamples, skip, first_frame = a_w, nframes = n_w and flags as bnflac_select_windows writes them.
+ *     An empty window is as there, with pcm_first = 0.
+ *   d_win_sel_first[w] (uint32, nwindows entries, may be NULL): rank_{a_w} for a window that is not
+ *     empty, else 0.  Over an index's tables window w's records are [that, that + nframes) of
+ *     d_sel_info: their status / crc_ok can be read there after the decode.
+ *   d_sel_totals (uint64[2], 8-byte aligned): {F, S}; S is the sample frames of the shared compact PCM.
+ *   d_status (4 words): [0] bit 0 F > sel_cap (the records below sel_cap are exactly right, every
+ *     window record is written from the true positions, a window whose records all lie below sel_cap
+ *     is complete), bit 1 unusable tables, bit 2 some request names no stream; [1] F (at most cap:
+ *     nothing saturates); [2] windows that are not empty; [3] windows clipped.
+ * nwindows == 0 writes a zero status, zero totals and the filler.
+ * Over tables bnflac_index_streams wrote, the frames of a stream tile it, so a window's run is
+ * contiguous in rank and in pos with the spacing out_sample had: window w read through d_windows[w]
+ * is byte-identical to what the bnflac_select_windows chain yields for it.  Over any other contents
+ * the call returns some windows and never faults; no trip count is a table value.
+ * A negative return (nothing launched, nothing written): the refusals of bnflac_select_windows, and
+ * d_sel_totals not 8-byte aligned.
+ * Grids, loop bounds and scratch sizes depend on cap, nwindows and sel_cap only (a workgroup past the
+ * last position any window covers leaves at once).  Nothing at or past position cap of the index's
+ * tables is read, and d_info only at positions of M; nothing at or past sel_cap (records, offsets),
+ * nwindows (d_windows, d_win_sel_first) or entry 2 of the totals is written.  Asynchronous on
+ * hip_stream, no host synchronisation, on ctx's device; the only allocation is bnflac_select_ranges'
+ * scratch in ctx, which never shrinks: 16 bytes per position of [0, cap] plus 16 per 1,024 positions,
+ * nothing per window (the window records are completed in place).  With bnflac_index_streams' cap a
+ * bound from the buffer's size, that is the price of the call: pass the index's frame count (known
+ * after one read-back) as cap where the memory matters. */
+BNFLAC_API int bnflac_select_windows_shared(bnflac_ctx *ctx, const uint64_t *d_frame_offsets,
+                                            const bnflac_frame_info *d_info, uint32_t cap,
+                                            const uint32_t *d_stream_frames, const uint64_t *d_stream_samples,
+                                            uint32_t nstreams, const bnflac_window_request *d_requests, uint32_t nwindows,
+                                            uint64_t *d_sel_offsets, bnflac_frame_info *d_sel_info, uint32_t sel_cap,
+                                            bnflac_window *d_windows, uint32_t *d_win_sel_first, uint64_t *d_sel_totals,
+                                            uint32_t *d_status, void *hip_stream);
+
+/* The same selection over tables in host memory, with the same results; no GPU needed.  0, or -1
+ * for a null argument, nwindows >= 2^30 or no memory for cap + 1 marks. */
+BNFLAC_API int bnflac_select_windows_shared_host(const bnflac_frame_info *info, uint32_t cap,
+                                                 const uint32_t *stream_frames, const uint64_t *stream_samples,
+                                                 uint32_t nstreams, const bnflac_window_request *requests,
+                                                 uint32_t nwindows, bnflac_frame_info *sel_info, uint32_t sel_cap,
+                                                 bnflac_window *windows, uint32_t *win_sel_first, uint64_t sel_totals[2],
+                                                 uint32_t status[4]);
 
 /* The windows of a decoded selection as rows of one shape.  With stride = bnflac_out_stride(
  * out_format, sp), row s starts at d_rows + s * row_bytes: its first min(d_windows[s].nsamples,
