@@ -32,6 +32,7 @@
 #include "bnf_crc16.h"
 #include "bnf_crc16_tab.h"
 #include "bnf_frame.h"
+#include "bnf_out_range.h" /* a frame is written only when its whole range lies inside the output */
 #include "bnf_residual.h"
 
 /* ------------------------------------------------------ wave-uniform bit reader */
@@ -1218,19 +1219,17 @@ __global__ void __launch_bounds__(64) k_fill_bad(const bnf_frame_info *__restric
         if ((st == BNF_ST_ERROR || st == BNF_ST_TRUNC) && info[f].sub_start[0] != 0u) {
             const uint32_t C = info[f].channels, bsz = info[f].blocksize;
             const uint64_t os = info[f].out_sample;
+            uint64_t stride; /* the decode kernels' */
             switch (fmt) {
+            case BNF_OUT_PLANAR32: case BNF_OUT_INTERLEAVED32: stride = 4ull * sp.channels; break;
+            case BNF_OUT_FLACDECODER: stride = C == 2 ? 4u : 2u; break;
+            default: stride = (uint64_t)sp.channels * (sp.bps == 24 ? 3u : 2u); break;
+            }
+            start = os * stride; /* exact for a position in range */
             /* the frame's own slot only: a planar frame with more channels than sp.channels
              * would reach into the next frame's slot, so the fill stops at sp.channels */
-            case BNF_OUT_PLANAR32: start = os * sp.channels * 4u; n = (uint64_t)min(C, sp.channels) * bsz * 4u; break;
-            case BNF_OUT_INTERLEAVED32: start = os * sp.channels * 4u; n = (uint64_t)sp.channels * bsz * 4u; break;
-            case BNF_OUT_FLACDECODER: start = os * (C == 2 ? 4u : 2u); n = (uint64_t)bsz * (C == 2 ? 4u : 2u); break;
-            default: {
-                const uint32_t fb = sp.bps == 24 ? 3u : 2u;
-                start = os * sp.channels * fb;
-                n = (uint64_t)bsz * sp.channels * fb;
-            }
-            }
-            bad = n != 0 && start <= out_bytes && n <= out_bytes - start;
+            n = fmt == BNF_OUT_PLANAR32 ? (uint64_t)min(C, sp.channels) * bsz * 4u : (uint64_t)bsz * stride;
+            bad = n != 0 && bnf_out_in_range(os, bsz, bnf_out_limit(out_bytes, stride));
         }
     }
     uint64_t m = __ballot(bad);
@@ -1590,7 +1589,7 @@ DEV void decode_block(uint32_t blk, uint32_t *ring, int32_t *lds, const uint32_t
             case BNF_OUT_FLACDECODER: stride = fi.channels == 2 ? 4u : 2u; break;
             default: stride = (uint64_t)sp.channels * (sp.bps == 24 ? 3u : 2u); break;
             }
-            if (frame_ok && (fi.out_sample + fi.blocksize) * stride > out_bytes) {
+            if (frame_ok && !bnf_out_in_range(fi.out_sample, fi.blocksize, bnf_out_limit(out_bytes, stride))) {
                 ok = 0;
                 fi.status = BNF_ST_SKIPPED;
                 fi.flags |= 2u;
@@ -3363,7 +3362,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_st(const uint32_t *__restrict_
     else { stride = 4ull * sp.channels; ok = ok && sp.channels == 2; }
     const uint32_t bs = ok ? fi.blocksize : 0u;
     const uint64_t os = ok ? fi.out_sample : 0u;
-    ok = ok && (os + bs) * stride <= out_bytes;
+    ok = ok && bnf_out_in_range(os, bs, bnf_out_limit(out_bytes, stride)); /* the limit is wave-uniform */
     uint8_t *dst = out + os * stride; /* the frame's first byte (planar: channel 0's) */
     const bool al = (((uintptr_t)dst) & 15u) == 0 && (FMT != BNF_OUT_PLANAR32 || (bs & 3u) == 0);
 
@@ -3993,7 +3992,7 @@ __global__ void __launch_bounds__(64, 2) k_decode_sw(const uint32_t *__restrict_
     if (FMT == BNF_OUT_FILEREADER) { stride = 6; ok = ok && sp.bps == 24; }
     const uint32_t bs = ok ? fi.blocksize : 0u;
     const uint64_t os = ok ? fi.out_sample : 0u;
-    ok = ok && (os + bs) * stride <= out_bytes;
+    ok = ok && bnf_out_in_range(os, bs, bnf_out_limit(out_bytes, stride)); /* the limit is wave-uniform */
     uint8_t *dst = out + os * stride;
     /* timing ablation 0x10000000: every wave stores into one 64 KB window (same store
      * instructions, an L2-resident footprint); output is wrong */

@@ -47,6 +47,7 @@
  */
 #include "bnf_crc16_tab.h"
 #include "bnf_frame.h"
+#include "bnf_out_range.h"
 #include "bnf_residual.h"
 
 #define SYS_CHK 32                   /* samples per chunk: one s_barrier per chunk */
@@ -660,7 +661,7 @@ __global__ void __launch_bounds__(SYS_THREADS) k_decode_sys(const uint32_t *__re
             case BNF_OUT_FLACDECODER: stride = fi.channels == 2 ? 4u : 2u; break;
             default: stride = (uint64_t)sp.channels * (sp.bps == 24 ? 3u : 2u); break;
             }
-            const bool past = (fi.out_sample + fi.blocksize) * stride > out_bytes;
+            const bool past = !bnf_out_in_range(fi.out_sample, fi.blocksize, bnf_out_limit(out_bytes, stride));
             if (unsupported || past) {
                 ok = false;
                 info[f].status = BNF_ST_SKIPPED;

@@ -264,8 +264,19 @@ BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
 /* Decode nframes frames starting at d_frame_offsets (byte offsets into d_bytes).
  * Output position of each frame: d_out_sample[i] if non-NULL, else the header's
  * sample number (frame number x STREAMINFO blocksize for fixed-blocksize streams) minus
- * base_sample.  Frames that would end past out_bytes are not written (status 3,
- * flags bit 1).  d_info receives one record per frame.  A frame whose status is not OK
+ * base_sample.  A frame is written only when its whole range lies in [0, out_bytes): with
+ * stride = bnflac_out_stride (BNFLAC_OUT_FLACDECODER: by the frame's own channels) and
+ * limit = out_bytes / stride, a frame of blocksize b at position p is written iff p <= limit
+ * and b <= limit - p.  Positions are 64-bit and nothing in the rule wraps: a header number
+ * below base_sample (the difference is taken modulo 2^64), or a table value whose byte range
+ * does not fit (one near 2^64, one whose byte offset passes 2^64), is out of range like a frame
+ * that ends past out_bytes: not one byte is written, status 3, flags bit 1.  The same rule
+ * decides the zero-fill below.  d_out must be 4-byte aligned (the int32 layouts and the
+ * 2-channel 16-bit layouts store whole dwords at multiples of 4 from d_out); any device
+ * allocation is.  Which store path a frame takes (16-byte, 4-byte or byte stores, whole 64- or
+ * 128-byte lines) follows its range's absolute address: the bytes never depend on it, the speed
+ * does, and is best when d_out and the frames' starts are 128-byte aligned.
+ * d_info receives one record per frame.  A frame whose status is not OK
  * (an error or truncation inside a subframe; libFLAC writes nothing for it) has its output
  * range zero-filled when its header parsed (sub_start[0] != 0), and is not written when the
  * header itself failed (no range).  A CRC-16 mismatch is status OK with crc_ok 0 and a
