@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bnf_health.h"
 #include "bnf_select.h"
 #include "bnflac_device.h"
 
@@ -267,6 +268,18 @@ hipError_t bnf_launch_gather_ranges(const uint8_t *pcm, uint64_t pcm_bytes, uint
 hipError_t bnf_launch_gather_f32(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, uint32_t unit, uint32_t bps,
                                  uint32_t channels, uint32_t flags, const bnf_window *windows, uint32_t nstreams,
                                  uint32_t row_samples, uint64_t plane_pitch, float *out, uint32_t *status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_health.hip (no tables, no g_stats, no ablate word)
+ * k_hl_*: the rule of bnf_health.h over the records of a decoded selection (sel_info 16-byte aligned),
+ * its window table and the position of each window's first record.  requests, streams and
+ * stream_samples are all nullptr or all given.  scratch: bnf_window_health_scratch_bytes(sel_cap,
+ * nwindows) bytes, 16-byte aligned: 24 bytes per position of [0, sel_cap) and 24 per 1,024 positions
+ * plus 24 (24 bytes when nwindows is 0).  Zeroes status (4 words) on s, then launches. */
+uint64_t bnf_window_health_scratch_bytes(uint32_t sel_cap, uint32_t nwindows);
+hipError_t bnf_launch_window_health(const bnf_frame_info *sel_info, uint32_t sel_cap, const bnf_window *windows,
+                                    const uint32_t *first, uint32_t nwindows, const bnf_window_request *requests,
+                                    const bnf_stream_desc *streams, const uint64_t *stream_samples, uint32_t nstreams,
+                                    bnf_window_health *health, uint32_t *status, void *scratch, hipStream_t s);
 } /* extern "C" */
 
 #endif

@@ -693,6 +693,63 @@ extern "C" BNFLAC_API int bnflac_select_windows_shared_host(const bnflac_frame_i
     return 0;
 }
 
+static_assert(sizeof(bnflac_window_health_rec) == sizeof(bnf_window_health) && sizeof(bnf_window_health) == 32 &&
+                  offsetof(bnflac_window_health_rec, bad_samples) == 16 && offsetof(bnf_window_health, bad_samples) == 16 &&
+                  offsetof(bnflac_window_health_rec, missing) == 24 && offsetof(bnf_window_health, missing) == 24,
+              "window health record: 32 bytes, bad_samples @16, missing @24");
+static_assert(sizeof(bnflac_stream_desc) == sizeof(bnf_stream_desc) &&
+                  offsetof(bnflac_stream_desc, total_samples) == offsetof(bnf_stream_desc, total_samples),
+              "stream descriptor layout");
+static_assert((int)BNFLAC_HEALTH_DAMAGED == (int)BNF_HEALTH_DAMAGED && (int)BNFLAC_HEALTH_SHORT == (int)BNF_HEALTH_SHORT &&
+                  (int)BNFLAC_HEALTH_UNKNOWN == (int)BNF_HEALTH_UNKNOWN && (int)BNFLAC_HEALTH_EMPTY == (int)BNF_HEALTH_EMPTY &&
+                  (int)BNFLAC_HEALTH_NO_STREAM == (int)BNF_HEALTH_NO_STREAM,
+              "window health flags");
+
+extern "C" BNFLAC_API int bnflac_window_health(bnflac_ctx *ctx, const bnflac_frame_info *d_sel_info, uint32_t sel_cap,
+                                               const bnflac_window *d_windows, const uint32_t *d_first, uint32_t nwindows,
+                                               const bnflac_window_request *d_requests, const bnflac_stream_desc *d_streams,
+                                               const uint64_t *d_stream_samples, uint32_t nstreams,
+                                               bnflac_window_health_rec *d_health, uint32_t *d_status, void *hs) {
+    if (!ctx) return fail("bnflac_window_health: null ctx");
+    DevGuard dg(ctx->device); /* launches and scratch on the context's device */
+    if (!d_health || !d_status) return fail("bnflac_window_health: null output");
+    if (!d_sel_info || !d_windows || !d_first) return fail("bnflac_window_health: null table");
+    if ((!d_requests || !d_streams || !d_stream_samples) && (d_requests || d_streams || d_stream_samples))
+        return fail("bnflac_window_health: d_requests, d_streams and d_stream_samples are all given or all null");
+    if (((uintptr_t)d_sel_info) & 15u) return fail("bnflac_window_health: d_sel_info must be 16-byte aligned");
+    if ((((uintptr_t)d_windows) | ((uintptr_t)d_requests) | ((uintptr_t)d_streams) | ((uintptr_t)d_stream_samples) |
+         ((uintptr_t)d_health)) & 7u)
+        return fail("bnflac_window_health: the 64-bit tables must be 8-byte aligned");
+    if ((((uintptr_t)d_first) | ((uintptr_t)d_status)) & 3u)
+        return fail("bnflac_window_health: the 32-bit tables must be 4-byte aligned");
+    if (nwindows >= (1u << 30)) return fail("bnflac_window_health: too many windows");
+    /* the scratch of bnflac_select_ranges, which only ever grows: 24 bytes per position of the selection */
+    if (!ctx->sel.grow(std::max<size_t>((size_t)bnf_window_health_scratch_bytes(sel_cap, nwindows), 65536)))
+        return fail("bnflac_window_health: out of device memory");
+    hipError_t e = bnf_launch_window_health((const bnf_frame_info *)d_sel_info, sel_cap, (const bnf_window *)d_windows, d_first,
+                                            nwindows, (const bnf_window_request *)d_requests,
+                                            (const bnf_stream_desc *)d_streams, d_stream_samples, nstreams,
+                                            (bnf_window_health *)d_health, d_status, ctx->sel.p, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_window_health: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_window_health_host(const bnflac_frame_info *sel_info, uint32_t sel_cap,
+                                                    const bnflac_window *windows, const uint32_t *first, uint32_t nwindows,
+                                                    const bnflac_window_request *requests, const bnflac_stream_desc *streams,
+                                                    const uint64_t *stream_samples, uint32_t nstreams,
+                                                    bnflac_window_health_rec *health, uint32_t status[4]) {
+    if (!health || !status) return fail("bnflac_window_health_host: null output");
+    if (!sel_info || !windows || !first) return fail("bnflac_window_health_host: null table");
+    if ((!requests || !streams || !stream_samples) && (requests || streams || stream_samples))
+        return fail("bnflac_window_health_host: requests, streams and stream_samples are all given or all null");
+    if (nwindows >= (1u << 30)) return fail("bnflac_window_health_host: too many windows");
+    if (!bnf_window_health_host((const bnf_frame_info *)sel_info, sel_cap, (const bnf_window *)windows, first, nwindows,
+                                (const bnf_window_request *)requests, (const bnf_stream_desc *)streams, stream_samples,
+                                nstreams, (bnf_window_health *)health, status))
+        return fail("bnflac_window_health_host: out of memory");
+    return 0;
+}
+
 extern "C" BNFLAC_API int bnflac_gather_ranges(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
                                                const bnflac_stream_params *sp, const bnflac_window *d_windows,
                                                uint32_t nstreams, uint32_t row_samples, uint64_t row_bytes, uint8_t *d_rows,

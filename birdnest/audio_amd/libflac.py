@@ -131,6 +131,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_select_ranges", "bnflac_select_ranges_host", "bnflac_gather_ranges",
                  "bnflac_select_windows", "bnflac_select_windows_host",
                  "bnflac_select_windows_shared", "bnflac_select_windows_shared_host",
+                 "bnflac_window_health", "bnflac_window_health_host",
                  "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
@@ -241,6 +242,10 @@ def load() -> ctypes.CDLL:
     L.bnflac_select_windows_shared_host.restype = i
     L.bnflac_select_windows_shared_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, ctypes.c_uint32, p,
                                                     ctypes.c_uint32, p, p, p, p]
+    L.bnflac_window_health.restype = i
+    L.bnflac_window_health.argtypes = [p, p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, p, ctypes.c_uint32, p, p, p]
+    L.bnflac_window_health_host.restype = i
+    L.bnflac_window_health_host.argtypes = [p, ctypes.c_uint32, p, p, ctypes.c_uint32, p, p, p, ctypes.c_uint32, p, p]
     L.bnflac_gather_ranges.restype = i
     L.bnflac_gather_ranges.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                        p, p, p]
@@ -539,6 +544,65 @@ def select_windows_shared_host(info: np.ndarray, cap: int, stream_frames, stream
     return sel, win, first, totals, status
 
 
+class WindowHealth(ctypes.Structure):
+    """bnflac_window_health_rec: one window's record of window_health."""
+    _fields_ = [("flags", ctypes.c_uint32), ("bad_frames", ctypes.c_uint32), ("crc_frames", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("bad_samples", ctypes.c_uint64), ("missing", ctypes.c_uint64)]
+
+
+WINDOW_HEALTH_BYTES = 32
+WINDOW_HEALTH_DTYPE = np.dtype([("flags", "<u4"), ("bad_frames", "<u4"), ("crc_frames", "<u4"), ("reserved", "<u4"),
+                                ("bad_samples", "<u8"), ("missing", "<u8")])
+assert WINDOW_HEALTH_DTYPE.itemsize == ctypes.sizeof(WindowHealth) == WINDOW_HEALTH_BYTES
+# WindowHealth.flags; the first three are also the bits of window_health's status word 0
+HEALTH_DAMAGED, HEALTH_SHORT, HEALTH_UNKNOWN, HEALTH_EMPTY, HEALTH_NO_STREAM = 1, 2, 4, 8, 16
+
+
+def health_array(raw: np.ndarray) -> np.ndarray:
+    """View a uint8 buffer of window_health records as a structured array."""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=WINDOW_HEALTH_DTYPE)
+
+
+def window_health_host(sel_info: np.ndarray, sel_cap: int, windows: np.ndarray, first, requests=None, streams=None,
+                       stream_samples=None):
+    """window_health over host tables (bnflac_window_health_host, no GPU).  sel_info: the selection's
+    FRAME_INFO_DTYPE records after the decode (at least sel_cap); windows: its WINDOW_DTYPE table;
+    first: per window the position of its first record (sel_frames of select_ranges_host /
+    select_windows_host, whose entries past the windows are ignored, or win_sel_first of
+    select_windows_shared_host).  requests, streams, stream_samples: all None, or the requests the
+    selection was made from ([(stream, first_sample[, nsamples])] or a WINDOW_REQUEST_DTYPE array), the
+    STREAM_DESC_DTYPE table the scan completed and the index's stream_samples.
+    -> (health[k] in WINDOW_HEALTH_DTYPE, status uint32[4])"""
+    sel = np.ascontiguousarray(sel_info, dtype=FRAME_INFO_DTYPE)
+    win = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+    k = len(win)
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    if len(sel) < sel_cap or len(f) < k:
+        raise ValueError("sel_info holds sel_cap records, first one entry per window")
+    given = [x is not None for x in (requests, streams, stream_samples)]
+    if any(given) and not all(given):
+        raise ValueError("requests, streams and stream_samples are all given or all None")
+    r = sd = ss = None
+    n = 0
+    if all(given):
+        r = requests if isinstance(requests, np.ndarray) and requests.dtype == WINDOW_REQUEST_DTYPE else window_requests(requests)
+        r = np.ascontiguousarray(r)
+        sd = np.ascontiguousarray(streams, dtype=STREAM_DESC_DTYPE)
+        ss = np.ascontiguousarray(stream_samples, dtype=np.uint64)
+        n = len(sd)
+        if len(r) != k or len(ss) != n + 1:
+            raise ValueError("one request per window, and stream_samples holds nstreams + 1 entries")
+    health, status = np.zeros(k, dtype=WINDOW_HEALTH_DTYPE), np.zeros(4, np.uint32)
+    # a table without entries still needs an address: the call refuses null pointers
+    vp = lambda a: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(ctypes.c_void_p)
+    rc = load().bnflac_window_health_host(vp(sel), sel_cap, vp(win), vp(f), k, vp(r) if r is not None else None,
+                                          vp(sd) if r is not None else None, vp(ss) if r is not None else None, n,
+                                          vp(health), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return health, status
+
+
 def stream_table(streams, nbytes: int) -> np.ndarray:
     """The descriptor table of index_streams from [(begin, end, first_offset, total_samples)],
     checked as the library checks it (its status bit 2): ValueError for a range that is
@@ -631,11 +695,24 @@ class Corpus:
     same stream, or the caller's events)."""
 
     def __init__(self, d_bytes, nbytes, sp, nstreams, cap, d_offsets, d_info, d_stream_frames, d_stream_samples,
-                 scan_status, index_status):
+                 scan_status, index_status, d_streams=None):
         self.d_bytes, self.nbytes, self.sp, self.nstreams, self.cap = d_bytes, nbytes, sp, nstreams, cap
         self.d_offsets, self.d_info = d_offsets, d_info
         self.d_stream_frames, self.d_stream_samples = d_stream_frames, d_stream_samples
         self.scan_status, self.index_status = scan_status, index_status  # device int32[4] each, not synchronised
+        self.d_streams = d_streams  # scan_streams' descriptor table, int64[nstreams * 4], or None
+
+    def missing_samples(self):
+        """Per stream, the sample frames STREAMINFO promises and the index lacks (a damaged stream's
+        chain ends at the damage): total_samples minus the samples kept, 0 where the total is 0
+        (unknown, or the stream was emptied by the scan) or not above the samples kept.
+        -> device int64[nstreams], not synchronised."""
+        import torch
+        if self.d_streams is None:
+            raise ValueError("the corpus was made without the descriptor table (d_streams)")
+        total = self.d_streams.view(-1)[: 4 * self.nstreams].view(self.nstreams, 4)[:, 3]
+        kept = self.d_stream_samples[1: self.nstreams + 1] - self.d_stream_samples[: self.nstreams]
+        return torch.where((total != 0) & (total > kept), total - kept, torch.zeros_like(total))
 
 
 class BatchDecoder:
@@ -950,6 +1027,58 @@ class BatchDecoder:
             raise RuntimeError(self.L.bnflac_last_error().decode())
         return d_sel_offs, d_sel_info, d_win, d_first[:k], d_totals, d_status
 
+    def window_health(self, d_sel_info, sel_cap: int, d_windows, d_first, nwindows: int, requests=None, corpus=None,
+                      stream=None):
+        """Which windows of a decoded selection hold damaged or missing audio (bnflac_window_health),
+        after decode_parsed on the same stream.  d_sel_info, sel_cap, d_windows: the selection's records
+        and window table; d_first: the position of each window's first record, d_sel_frames of
+        select_ranges / select_windows or d_win_sel_first of select_windows_shared.
+        requests, corpus: both None (bad frames only: missing is 0, SHORT and NO_STREAM are never
+        set), or the requests the selection was made from ([(stream, first_sample[, nsamples])] or a
+        device tensor of 3 64-bit words per window) and the Corpus they name streams of, whose
+        descriptor table and sample bounds say what STREAMINFO promises and what the index kept.
+        -> (d_health uint8[nwindows * 32] for health_array, d_status int32[4]: bit 0 / 1 / 2 of word 0
+            some window DAMAGED / SHORT / UNKNOWN, then how many of each), on the device and not
+        synchronised."""
+        import torch
+        dev = d_sel_info.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if (requests is None) != (corpus is None):
+            raise ValueError("requests and corpus are both given or both None")
+        d_req = d_streams = d_ss = None
+        nstreams = 0
+        if requests is not None:
+            if corpus.d_streams is None:
+                raise ValueError("the corpus was made without the descriptor table (d_streams)")
+            d_streams, d_ss, nstreams = corpus.d_streams, corpus.d_stream_samples, corpus.nstreams
+            if isinstance(requests, torch.Tensor):
+                if not requests.is_cuda or requests.element_size() != 8 or requests.numel() % 3 or not requests.is_contiguous():
+                    raise ValueError("device requests are a contiguous CUDA tensor of 3 64-bit words per window")
+                d_req, k = requests, requests.numel() // 3
+            else:
+                table = window_requests(requests)
+                k = len(table)
+            if k != nwindows:
+                raise ValueError("one request per window")
+        if d_first.numel() < nwindows or d_first.element_size() != 4:
+            raise ValueError("d_first holds one 32-bit position per window")
+        with torch.cuda.stream(s):
+            if requests is not None:
+                if d_req is None:
+                    d_req = torch.from_numpy(table.view(np.int64).reshape(-1)).to(dev)
+                # a table without entries still needs an address: the three are all given or all null
+                some = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+                d_req, d_streams = some(d_req), some(d_streams)
+            d_health = torch.zeros(max(nwindows, 1) * WINDOW_HEALTH_BYTES, dtype=torch.uint8, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self.L.bnflac_window_health(self.ctx, vp(d_sel_info), sel_cap, vp(d_windows), vp(d_first), nwindows,
+                                         vp(d_req), vp(d_streams), vp(d_ss), nstreams, vp(d_health), vp(d_status),
+                                         self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return d_health[: nwindows * WINDOW_HEALTH_BYTES], d_status
+
     def gather_ranges(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, row_samples: int,
                       row_bytes: Optional[int] = None, d_rows=None, stream=None, pcm_bytes=None):
         """The windows of a decoded selection as rows of one shape (bnflac_gather_ranges): row s is
@@ -1108,14 +1237,16 @@ class BatchDecoder:
         d_tab, _, _, st_scan = self.scan_streams(d_bytes, nbytes, ranges_bytes, expect=sp, stream=s)
         d_offs, _, d_info, d_sf, d_ss, st_index = self.index_streams(d_bytes, nbytes, d_tab, sp, cap, cand_cap=cand_cap,
                                                                      stream=s)
-        return Corpus(d_bytes, nbytes, sp, n, cap, d_offs, d_info, d_sf, d_ss, st_scan, st_index)
+        return Corpus(d_bytes, nbytes, sp, n, cap, d_offs, d_info, d_sf, d_ss, st_scan, st_index, d_tab)
 
     def _decode_crop_selection(self, corpus: Corpus, requests, nsamples, fmt, s, shared=False, max_frames=None,
-                               max_samples=None):
+                               max_samples=None, health=False):
         """The front of decode_crops and decode_crops_f32: select_windows over the corpus's index ->
         decode_parsed(nframes = sel_cap) of the copied records into a compact PCM in fmt, on stream s.
         shared: select_windows_shared in select_windows' place, with sel_cap = max_frames and a PCM of
         max_samples sample frames where they are given, and "totals" in the status.
+        health: window_health over the completed records, "health" and "windows_health" in the status;
+        the requests are uploaded once, for the selection and for it.
         -> (d_pcm, d_windows, nwindows, the PCM's bytes when shared else None, {"select" -> int32[4]})"""
         import torch
         sp = corpus.sp
@@ -1125,6 +1256,8 @@ class BatchDecoder:
             raise ValueError("OUT_PLANAR32 is channel-major per frame: a window of it is no byte range")
         if sp.min_blocksize < 1 or sp.max_blocksize < sp.min_blocksize:
             raise ValueError("sp must carry STREAMINFO's min_blocksize and max_blocksize")
+        if health and corpus.d_streams is None:
+            raise ValueError("health needs the corpus's descriptor table (d_streams): index_corpus keeps it")
         if isinstance(requests, torch.Tensor):
             k = requests.numel() // 3
         else:
@@ -1134,28 +1267,35 @@ class BatchDecoder:
         pcm_samples = k * (nsamples + 2 * (sp.max_blocksize - 1))
         stride = out_stride(fmt, sp)
         status = {}
+        if health and k and not isinstance(requests, torch.Tensor):
+            with torch.cuda.stream(s):
+                requests = torch.from_numpy(window_requests(requests).view(np.int64).reshape(-1)).to(corpus.d_bytes.device)
         if shared:  # the union is never larger than the sum, nor than the index
             sel_cap = min(sel_cap, corpus.cap) if max_frames is None else max_frames
             pcm_samples = pcm_samples if max_samples is None else max_samples
             if sel_cap < 0 or pcm_samples < 0:
                 raise ValueError("max_frames and max_samples are counts")
-            _, d_sel_info, d_win, _, status["totals"], status["select"] = self.select_windows_shared(
+            _, d_sel_info, d_win, d_first, status["totals"], status["select"] = self.select_windows_shared(
                 corpus.d_offsets, corpus.d_info, corpus.cap, corpus.d_stream_frames, corpus.d_stream_samples,
                 corpus.nstreams, requests, sel_cap, stream=s)
         else:
             if max_frames is not None or max_samples is not None:
                 raise ValueError("max_frames and max_samples size the shared selection: pass shared=True")
-            _, d_sel_info, _, _, d_win, status["select"] = self.select_windows(
+            _, d_sel_info, d_first, _, d_win, status["select"] = self.select_windows(
                 corpus.d_offsets, corpus.d_info, corpus.cap, corpus.d_stream_frames, corpus.d_stream_samples,
                 corpus.nstreams, requests, sel_cap, stream=s)
         with torch.cuda.stream(s):
             pcm_bytes = pcm_samples * stride
             d_pcm = torch.zeros(max((pcm_bytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=corpus.d_bytes.device)
         self.decode_parsed(corpus.d_bytes, corpus.nbytes, sel_cap, sp, fmt, d_pcm, d_sel_info, stream=s)
+        if health:
+            d_health, status["health"] = self.window_health(d_sel_info, sel_cap, d_win, d_first, k, requests, corpus,
+                                                            stream=s)
+            status["windows_health"] = d_health.view(k, WINDOW_HEALTH_BYTES)
         return d_pcm, d_win, k, pcm_bytes if shared else None, status
 
     def decode_crops(self, corpus: Corpus, requests, nsamples: int, fmt: int, stream=None, shared: bool = False,
-                     max_frames: Optional[int] = None, max_samples: Optional[int] = None):
+                     max_frames: Optional[int] = None, max_samples: Optional[int] = None, health: bool = False):
         """Any crops of nsamples sample frames out of an indexed corpus, as rows in request order:
         select_windows -> decode_parsed(nframes = sel_cap) -> gather_ranges over the index that
         index_corpus made, with no host synchronisation and nothing read back.
@@ -1173,14 +1313,19 @@ class BatchDecoder:
         where the caller knows the union's size; the defaults are the bounds above with sel_cap no
         larger than corpus.cap, which always suffice.  Too small a max_frames shows as bit 0 of the
         select status, a crop whose samples were not provided as a zero row and the gather status.
+        health: window_health after the decode, over the same uploaded requests: a frame that failed
+        to decode or failed its CRC leaves zeros in a row, and a stream whose index ends at damage
+        gives clipped or empty rows; the records say which crops and how many sample frames.  The
+        rows and the other status entries are what health=False gives.
         -> (rows, status): rows int32[k, nsamples, channels] for OUT_INTERLEAVED32, else
-        uint8[k, nsamples * stride]; status: {"select", "gather"} -> device int32[4], and with
-        shared "totals" -> device int64[2], the frames and sample frames selected."""
+        uint8[k, nsamples * stride]; status: {"select", "gather"} -> device int32[4], with
+        shared "totals" -> device int64[2], the frames and sample frames selected, and with health
+        "health" -> device int32[4] and "windows_health" -> device uint8[k, 32] (health_array)."""
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()
         sp = corpus.sp
         d_pcm, d_win, k, pcm_bytes, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s, shared,
-                                                                         max_frames, max_samples)
+                                                                         max_frames, max_samples, health)
         stride = out_stride(fmt, sp)
         d_rows, status["gather"] = self.gather_ranges(d_pcm, fmt, sp, d_win, k, nsamples, stream=s, pcm_bytes=pcm_bytes)
         with torch.cuda.stream(s):
@@ -1192,10 +1337,10 @@ class BatchDecoder:
 
     def decode_crops_f32(self, corpus: Corpus, requests, nsamples: int, fmt: Optional[int] = None, mono: bool = False,
                          stream=None, shared: bool = False, max_frames: Optional[int] = None,
-                         max_samples: Optional[int] = None):
+                         max_samples: Optional[int] = None, health: bool = False):
         """decode_crops with gather_ranges_f32 as its last step: the crops as float32 channel planes
         in [-1, 1), in request order.  fmt, mono: as for decode_windows_f32; shared, max_frames,
-        max_samples: as for decode_crops.
+        max_samples, health: as for decode_crops.
         -> (float32[k, planes, nsamples], status)"""
         import torch
         sp = corpus.sp
@@ -1204,7 +1349,7 @@ class BatchDecoder:
             raise ValueError("the layout's bytes are not the samples: gather_ranges_f32 cannot read it")
         s = stream if stream is not None else torch.cuda.current_stream()
         d_pcm, d_win, k, pcm_bytes, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s, shared,
-                                                                         max_frames, max_samples)
+                                                                         max_frames, max_samples, health)
         planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, k, nsamples, mono=mono, stream=s,
                                                           pcm_bytes=pcm_bytes)
         return planes, status

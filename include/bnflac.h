@@ -21,6 +21,8 @@
  * sampler's order), bnflac_select_windows takes bnflac_select_ranges' place over an index made once.
  * Where the crops overlap (sliding windows over whole recordings), bnflac_select_windows_shared takes
  * the same requests and selects every frame once, the windows pointing into one shared compact PCM.
+ * After the decode of any of these selections, bnflac_window_health says per window how much of it lies
+ * in frames that failed to decode or failed their CRC, and how much of the request the index lacks.
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -571,6 +573,81 @@ BNFLAC_API int bnflac_select_windows_shared_host(const bnflac_frame_info *info, 
                                                  uint32_t nwindows, bnflac_frame_info *sel_info, uint32_t sel_cap,
                                                  bnflac_window *windows, uint32_t *win_sel_first, uint64_t sel_totals[2],
                                                  uint32_t status[4]);
+
+/* Per-window result record of bnflac_window_health (32 bytes, 8-byte aligned), device-resident. */
+typedef struct {
+    uint32_t flags;        /* BNFLAC_HEALTH_* */
+    uint32_t bad_frames;   /* records of the window's run, below sel_cap, that are not good */
+    uint32_t crc_frames;   /* of those: status OK with crc_ok 0 */
+    uint32_t reserved;     /* 0 */
+    uint64_t bad_samples;  /* sample frames of the window that lie in records that are not good */
+    uint64_t missing;      /* sample frames the request asked for that STREAMINFO promises and the index lacks */
+} bnflac_window_health_rec;
+
+enum { BNFLAC_HEALTH_DAMAGED = 1, BNFLAC_HEALTH_SHORT = 2, BNFLAC_HEALTH_UNKNOWN = 4,
+       BNFLAC_HEALTH_EMPTY = 8, BNFLAC_HEALTH_NO_STREAM = 16 };
+
+/* Which windows of a decoded selection hold damaged or missing audio.  A frame that fails to decode
+ * or fails its CRC-16 leaves zeros in the compact PCM, and a stream the index cut short at its damage
+ * gives clipped or empty windows; neither shows in the rows, nor in the select and gather status
+ * words, which describe the tables.  This call reduces the completed records per window, after
+ * bnflac_decode_parsed on the same stream, with nothing read back.
+ * d_sel_info, sel_cap: the selection's records after the decode.  d_windows: its window table.
+ * d_first[w]: the position in d_sel_info of window w's first record -- d_sel_frames for
+ * bnflac_select_ranges and bnflac_select_windows (only its first nwindows entries are read),
+ * d_win_sel_first for bnflac_select_windows_shared.  d_requests, d_streams, d_stream_samples: all NULL
+ * (missing is then 0 everywhere, SHORT and NO_STREAM are never set), or the requests the selection was
+ * made from, the descriptor table bnflac_scan_streams completed and the index's d_stream_samples and
+ * nstreams (a bnflac_select_ranges caller builds {s, d_ranges[s]} as d_requests).
+ * A record is good iff status == 0 && crc_ok != 0, else bad; a bad record with status == 0 is a crc
+ * record.  Per window w, with W = d_windows[w], f = d_first[w], n = W.nframes:
+ *   the run R = [min(f, sel_cap), min(f + n, sel_cap)), the sum taken in 64 bits;
+ *   bad_frames, crc_frames = the bad and the crc records of R; A = the sum of blocksize over R, B =
+ *   the sum over the bad records of R (modulo 2^64);
+ *   head = W.skip if n > 0, f < sel_cap and record f is bad, else 0;
+ *   tail = A - W.skip - W.nsamples (modulo 2^64) if n > 0, f + n <= sel_cap and record f + n - 1 is
+ *   bad, else 0;  bad_samples = B - head - tail (modulo 2^64).
+ *   flags: UNKNOWN iff n > 0 and f + n > sel_cap (some of the window's records were not provided: what
+ *   lies below sel_cap is counted, no tail is taken); EMPTY = W.flags bit 1; DAMAGED iff bad_frames != 0.
+ * Over tables a selection wrote from an index and a decode completed, a stream's frames tile it, and
+ * bad_samples is exactly the number of the window's sample frames that lie inside bad frames (a window
+ * of one bad frame: W.nsamples).  Only status, crc_ok and blocksize of a record are read.
+ * With the request tables, t = d_requests[w].stream:  t >= nstreams sets NO_STREAM, missing is 0 and no
+ * table entry is read for t.  Else total = d_streams[t].total_samples, T = d_stream_samples[t + 1] -
+ * d_stream_samples[t], lo = first_sample, hi = first_sample + nsamples (saturating), promised =
+ * min(hi, total) - min(lo, total), have = min(hi, T) - min(lo, T), and missing = promised - have if
+ * total > T and promised > have, else 0; SHORT iff missing != 0.  total == 0 (unknown, or the stream
+ * was emptied by the scan, whose status says why) means nothing is missing.  A crop clipped by the
+ * stream's true end is not SHORT; one that reaches into what damage cut off is, also when its window is
+ * empty, which the row alone can never show.
+ * d_status (device, 4 words): [0] bit 0 some window is DAMAGED, bit 1 some is SHORT, bit 2 some is
+ * UNKNOWN; [1] windows DAMAGED; [2] windows SHORT; [3] windows UNKNOWN.  nwindows == 0 writes a zero
+ * status.
+ * A negative return (nothing launched, nothing written, the cause in bnflac_last_error()): a null ctx,
+ * d_sel_info, d_windows, d_first, d_health or d_status; only some of the three request tables given;
+ * d_sel_info not 16-byte aligned; d_windows, d_requests, d_streams, d_stream_samples or d_health not
+ * 8-byte aligned; d_first or d_status not 4-byte aligned; nwindows >= 2^30.
+ * Nothing at or past sel_cap of the records is read, nothing at or past nwindows of the window, first
+ * and request tables, nothing of d_streams or d_stream_samples for a t >= nstreams; nothing at or past
+ * nwindows records of d_health or 4 words of d_status is written.  Over any table contents the call
+ * returns some values and never faults: no grid, loop bound or scratch size is a table value, they
+ * depend on sel_cap and nwindows only (prefixes over the record positions, then one lane per window).
+ * Asynchronous on hip_stream, no host synchronisation, on ctx's device; the only allocation is
+ * bnflac_select_ranges' scratch in ctx, which never shrinks: 24 bytes per position of [0, sel_cap) plus
+ * 24 per 1,024 positions, nothing per window. */
+BNFLAC_API int bnflac_window_health(bnflac_ctx *ctx, const bnflac_frame_info *d_sel_info, uint32_t sel_cap,
+                                    const bnflac_window *d_windows, const uint32_t *d_first, uint32_t nwindows,
+                                    const bnflac_window_request *d_requests, const bnflac_stream_desc *d_streams,
+                                    const uint64_t *d_stream_samples, uint32_t nstreams,
+                                    bnflac_window_health_rec *d_health, uint32_t *d_status, void *hip_stream);
+
+/* The same records and status over tables in host memory, by the same code (csrc/bnf_health.h); no GPU
+ * needed.  Refuses what the device call refuses apart from ctx and pointer alignment.  0, or -1 for
+ * such an argument or no memory for sel_cap + 1 prefixes. */
+BNFLAC_API int bnflac_window_health_host(const bnflac_frame_info *sel_info, uint32_t sel_cap, const bnflac_window *windows,
+                                         const uint32_t *first, uint32_t nwindows, const bnflac_window_request *requests,
+                                         const bnflac_stream_desc *streams, const uint64_t *stream_samples,
+                                         uint32_t nstreams, bnflac_window_health_rec *health, uint32_t status[4]);
 
 /* The windows of a decoded selection as rows of one shape.  With stride = bnflac_out_stride(
  * out_format, sp), row s starts at d_rows + s * row_bytes: its first min(d_windows[s].nsamples,
