@@ -2186,7 +2186,8 @@ __global__ void __launch_bounds__(256) k_chain_emit(const uint64_t *__restrict__
  * the only ordering between workgroups.  The running sample count is taken over the
  * candidates (0 for the unmarked) and rebased at the stream's first candidate, which is the
  * scan restarted at the stream's first kept frame. */
-enum { MS_BAD = 0, MS_NCAND = 1, MS_N = 2, MS_CTL_WORDS = 4 }; /* ctl: bad table, candidates found, candidates used */
+enum { MS_BAD = BNF_MS_BAD, MS_NCAND = BNF_MS_NCAND, MS_N = BNF_MS_N, MS_CTL_WORDS = BNF_MS_CTL_WORDS }; /* ctl: bad table, candidates found, candidates used */
+static_assert(KEY_OK == BNF_MS_KEY_OK, "the key bit bnflac_resync.hip reads");
 #define MS_SCAN 1024u /* elements per workgroup of the three-launch scans */
 
 DEV uint32_t ms_n(const uint32_t *__restrict__ ctl) { return ctl[MS_N]; }
@@ -4798,13 +4799,10 @@ static void ms_scan_add(const uint32_t *c, const uint64_t *a, const uint32_t *n_
     hipLaunchKernelGGL(k_ms_add_apply, dim3(nb), dim3(MS_SCAN), 0, s, c, a, n_ptr, cap, csum, asum, co, ao);
 }
 
-/* The batched frame chain (see k_ms_check): sync scan, parse, keys, successors, pointer
- * doubling, EOS rule per stream and outputs, with no host synchronisation.  d_sf (nstreams + 1)
- * and d_status (4) are always written; d_ss may be null. */
-hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
-                                    bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
-                                    uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
-                                    uint32_t *d_status, hipStream_t s) {
+/* The front of the batched frame chain (see k_ms_check): the scratch presets, sync scan, parse,
+ * keys, successors and heads.  bnf_launch_chain_streams and the resync chain both start here. */
+hipError_t bnf_launch_chain_front(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
+                                  bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, hipStream_t s) {
     const uint32_t C = cand_cap, S = nstreams;
     const uint32_t B = bnf_scan_blocks(nbytes);
     const dim3 gc((C + 255u) / 256u), gs((S + 255u) / 256u), t256(256);
@@ -4832,12 +4830,35 @@ hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const
     hipLaunchKernelGGL(k_ms_keys_apply, dim3(nbc), dim3(MS_SCAN), 0, s, w.key, ctl, w.csum, w.info, w.seg, sd);
     hipLaunchKernelGGL(k_ms_succ, gc, t256, 0, s, w.cand, ctl, w.key, w.seg, sd, w.chi, w.jump, w.head);
     hipLaunchKernelGGL(k_ms_mark_heads, gs, t256, 0, s, w.head, S, ctl, w.mark);
-    /* 4. pointer doubling over all chains at once: 2^levels >= cand_cap */
+    return hipGetLastError();
+}
+
+/* 4. pointer doubling over all chains at once: 2^levels >= cand_cap */
+hipError_t bnf_launch_chain_jump(uint32_t cand_cap, bnf_ms_scratch w, hipStream_t s) {
+    const uint32_t C = cand_cap;
+    const dim3 gc((C + 255u) / 256u), t256(256);
+    const uint32_t *ctl = w.ctl;
     uint32_t levels = 1;
     while ((1ull << levels) < C) levels++;
     for (uint32_t k = 0; k < levels; k++)
         hipLaunchKernelGGL(k_ms_jump_mark, gc, t256, 0, s, w.jump + (size_t)(k & 1u) * C, w.jump + (size_t)((k + 1u) & 1u) * C,
                            w.mark, ctl);
+    return hipGetLastError();
+}
+
+/* The batched frame chain: the front, the pointer doubling, then the EOS rule per stream and the
+ * outputs, with no host synchronisation.  d_sf (nstreams + 1) and d_status (4) are always
+ * written; d_ss may be null. */
+hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
+                                    bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
+                                    uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
+                                    uint32_t *d_status, hipStream_t s) {
+    const uint32_t C = cand_cap, S = nstreams;
+    const dim3 gc((C + 255u) / 256u), gs((S + 255u) / 256u), t256(256);
+    const uint32_t *ctl = w.ctl;
+    hipError_t e = bnf_launch_chain_front(bytes, nbytes, sd, nstreams, sp, cand_cap, w, s);
+    if (e == hipSuccess) e = bnf_launch_chain_jump(cand_cap, w, s);
+    if (e != hipSuccess) return e;
     /* 5. positions and sample counts, kept frames per stream, the two prefixes over the streams */
     hipLaunchKernelGGL(k_ms_bs, gc, t256, 0, s, w.info, w.mark, ctl, w.bs);
     ms_scan_add(w.mark, w.bs, ctl + MS_N, C, w.csum, w.asum, w.pos, w.smp, s);

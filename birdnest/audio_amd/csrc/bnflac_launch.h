@@ -13,8 +13,14 @@
 #include <stdint.h>
 
 #include "bnf_health.h"
+#include "bnf_resync.h"
 #include "bnf_select.h"
 #include "bnflac_device.h"
+
+/* The batched chain's control words (bnf_ms_scratch.ctl: bad table, candidates found, candidates
+ * used) and the key bit of a valid frame start, as the kernels of two translation units read them. */
+enum { BNF_MS_BAD = 0, BNF_MS_NCAND = 1, BNF_MS_N = 2, BNF_MS_CTL_WORDS = 4 };
+#define BNF_MS_KEY_OK 0x10000u
 
 /* ------------------------------------------------------------- the `ablate` word
  * Every decode and parse kernel takes one uint32_t `ablate`.  It carries two disjoint fields:
@@ -201,6 +207,37 @@ hipError_t bnf_launch_chain_streams(const uint8_t *bytes, uint64_t nbytes, const
                                     bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, uint64_t *d_offs,
                                     uint64_t *d_os, bnf_frame_info *d_info, uint32_t cap, uint32_t *d_sf, uint64_t *d_ss,
                                     uint32_t *d_status, hipStream_t s);
+/* The two leading parts of bnf_launch_chain_streams, which the resync chain shares with it.
+ * front: the scratch presets and steps 1-3 (candidates, owners, records, keys, w.jump[0, C) = the
+ * CRC-16 successors, w.head, the heads marked in w.mark).  jump: step 4, the pointer doubling
+ * over whatever successor array w.jump[0, C) holds, growing w.mark along it. */
+hipError_t bnf_launch_chain_front(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd, uint32_t nstreams,
+                                  bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w, hipStream_t s);
+hipError_t bnf_launch_chain_jump(uint32_t cand_cap, bnf_ms_scratch w, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_resync.hip (no tables, no g_stats, no ablate word)
+ * k_rs_*: the rule of bnf_resync.h after bnf_launch_chain_front, on the same scratch w plus r (carved
+ * by bnf_resync_carve from memory of bnf_resync_scratch_bytes(cand_cap, nstreams) bytes, 16-byte
+ * aligned).  d_offs, d_os, d_info may be nullptr when cap is 0, d_os, d_info, d_ss and d_resync at
+ * any time.  r.ct keeps the candidate table of the call (bnflac_debug_index_candidates). */
+typedef struct {
+    bnf_index_cand *ct;                                        /* C */
+    uint64_t *p, *va, *vb, *vs, *gapv, *lv, *rc, *sc, *rp, *sq; /* C + 1 each */
+    uint64_t *bsum;                                            /* max(C, S) / 1024 + 2 */
+    int32_t *ext;                                              /* C */
+    uint32_t *why;                                             /* C */
+    int32_t *cut;                                              /* S */
+    uint32_t *segs, *rflags;                                   /* S each */
+    uint64_t *gapc, *base;                                     /* S each */
+    uint64_t *acc;                                             /* 2: placeholders, status bits */
+} bnf_rs_scratch;
+uint64_t bnf_resync_scratch_bytes(uint32_t cand_cap, uint32_t nstreams);
+bnf_rs_scratch bnf_resync_carve(void *mem, uint32_t cand_cap, uint32_t nstreams);
+hipError_t bnf_launch_chain_streams_resync(const uint8_t *bytes, uint64_t nbytes, const bnf_stream_desc *sd,
+                                           uint32_t nstreams, bnf_stream_params sp, uint32_t cand_cap, bnf_ms_scratch w,
+                                           bnf_rs_scratch r, uint64_t *d_offs, uint64_t *d_os, bnf_frame_info *d_info,
+                                           uint32_t cap, uint32_t *d_sf, uint64_t *d_ss, bnf_resync_rec *d_resync,
+                                           uint32_t *d_status, hipStream_t s);
 
 /* ------------------------------------------------------------- bnflac_md5.hip (no tables, no g_stats, no ablate word)
  * k_md5_streams: stream s is the sample frames [bounds[s], bounds[s + 1]) of pcm, `unit` bytes

@@ -173,6 +173,10 @@ struct bnflac_ctx {
     /* bnflac_index_stream scratch */
     CtxBuf cand, info, gap, jump, mark, pos, bs, small;
     CtxBuf ms; /* bnflac_index_streams scratch (bnf_ms_scratch, one allocation) */
+    /* the candidate table the last bnflac_index_streams_resync left in ms, and the control words
+     * that hold its length (nullptr: none) */
+    const bnf_index_cand *rs_ct = nullptr;
+    const uint32_t *rs_ctl = nullptr;
     CtxBuf sel; /* bnflac_select_ranges scratch (flags and workgroup sums) */
     CtxBuf order, porder; /* decode / parse order: histogram + permutation (k_order_*) */
     /* k_parse's CRC-16 hand-off of the last bnflac_parse_frames batch (8 words per frame), and
@@ -408,6 +412,49 @@ extern "C" BNFLAC_API int bnflac_index_stream(bnflac_ctx *ctx, const uint8_t *d_
 
 static_assert(sizeof(bnflac_stream_desc) == sizeof(bnf_stream_desc), "stream descriptor layout");
 
+/* The scratch of the batched chain, sized on the host from cand_cap, nstreams and nbytes: every
+ * array starts on a 16-byte boundary of one allocation (ctx->ms); `extra` more bytes behind them
+ * at *extra_p.  false: out of device memory. */
+static bool ms_scratch(bnflac_ctx *ctx, size_t C, size_t S, uint64_t nbytes, size_t extra, bnf_ms_scratch &w,
+                       uint8_t **extra_p) {
+    const size_t B = bnf_scan_blocks(nbytes);
+    const size_t nsum = std::max(B, std::max(C, S)) / 1024 + 2;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t o_ctl = take(16), o_blk = take(4 * (B + 1)), o_csum = take(4 * nsum), o_asum = take(8 * nsum),
+                 o_cand = take(8 * C), o_info = take(sizeof(bnf_frame_info) * C), o_seg = take(4 * C), o_key = take(4 * C),
+                 o_mark = take(4 * C), o_pos = take(4 * (C + 1)), o_bs = take(8 * C), o_smp = take(8 * (C + 1)),
+                 o_jump = take(8 * C), o_clo = take(4 * S), o_chi = take(4 * S), o_kept = take(4 * S), o_head = take(4 * S),
+                 o_ssum = take(8 * S), o_ss = take(8 * (S + 1)), o_extra = take(extra);
+    if (!ctx->ms.grow(off)) return false;
+    uint8_t *m = (uint8_t *)ctx->ms.p;
+    w.ctl = (uint32_t *)(m + o_ctl);
+    w.blk = (uint32_t *)(m + o_blk);
+    w.csum = (uint32_t *)(m + o_csum);
+    w.asum = (uint64_t *)(m + o_asum);
+    w.cand = (uint64_t *)(m + o_cand);
+    w.info = (bnf_frame_info *)(m + o_info);
+    w.seg = (int32_t *)(m + o_seg);
+    w.key = (uint32_t *)(m + o_key);
+    w.mark = (uint32_t *)(m + o_mark);
+    w.pos = (uint32_t *)(m + o_pos);
+    w.bs = (uint64_t *)(m + o_bs);
+    w.smp = (uint64_t *)(m + o_smp);
+    w.jump = (int32_t *)(m + o_jump);
+    w.clo = (uint32_t *)(m + o_clo);
+    w.chi = (uint32_t *)(m + o_chi);
+    w.kept = (uint32_t *)(m + o_kept);
+    w.head = (int32_t *)(m + o_head);
+    w.ssum = (uint64_t *)(m + o_ssum);
+    w.ss = (uint64_t *)(m + o_ss);
+    if (extra_p) *extra_p = m + o_extra;
+    return true;
+}
+
 extern "C" BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
                                                const bnflac_stream_desc *d_streams, uint32_t nstreams,
                                                const bnflac_stream_params *sp, uint32_t cand_cap,
@@ -430,49 +477,107 @@ extern "C" BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d
     }
     const uint64_t C64 = cand_cap ? cand_cap : nbytes / 1024 + 4096;
     if (C64 >= (1u << 30)) return fail("bnflac_index_streams: cand_cap too large");
-    /* scratch, sized on the host from cand_cap, nstreams and nbytes: every array starts on a
-     * 16-byte boundary of one allocation */
-    const size_t C = (size_t)C64, S = nstreams, B = bnf_scan_blocks(nbytes);
-    const size_t nsum = std::max(B, std::max(C, S)) / 1024 + 2;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 15) & ~(size_t)15;
-        return at;
-    };
-    const size_t o_ctl = take(16), o_blk = take(4 * (B + 1)), o_csum = take(4 * nsum), o_asum = take(8 * nsum),
-                 o_cand = take(8 * C), o_info = take(sizeof(bnf_frame_info) * C), o_seg = take(4 * C), o_key = take(4 * C),
-                 o_mark = take(4 * C), o_pos = take(4 * (C + 1)), o_bs = take(8 * C), o_smp = take(8 * (C + 1)),
-                 o_jump = take(8 * C), o_clo = take(4 * S), o_chi = take(4 * S), o_kept = take(4 * S), o_head = take(4 * S),
-                 o_ssum = take(8 * S), o_ss = take(8 * (S + 1));
-    if (!ctx->ms.grow(off)) return fail("bnflac_index_streams: out of device memory");
-    uint8_t *m = (uint8_t *)ctx->ms.p;
+    const size_t C = (size_t)C64;
     bnf_ms_scratch w;
-    w.ctl = (uint32_t *)(m + o_ctl);
-    w.blk = (uint32_t *)(m + o_blk);
-    w.csum = (uint32_t *)(m + o_csum);
-    w.asum = (uint64_t *)(m + o_asum);
-    w.cand = (uint64_t *)(m + o_cand);
-    w.info = (bnf_frame_info *)(m + o_info);
-    w.seg = (int32_t *)(m + o_seg);
-    w.key = (uint32_t *)(m + o_key);
-    w.mark = (uint32_t *)(m + o_mark);
-    w.pos = (uint32_t *)(m + o_pos);
-    w.bs = (uint64_t *)(m + o_bs);
-    w.smp = (uint64_t *)(m + o_smp);
-    w.jump = (int32_t *)(m + o_jump);
-    w.clo = (uint32_t *)(m + o_clo);
-    w.chi = (uint32_t *)(m + o_chi);
-    w.kept = (uint32_t *)(m + o_kept);
-    w.head = (int32_t *)(m + o_head);
-    w.ssum = (uint64_t *)(m + o_ssum);
-    w.ss = (uint64_t *)(m + o_ss);
+    ctx->rs_ct = nullptr; /* the scratch is reused: no candidate table of a resync call any more */
+    if (!ms_scratch(ctx, C, nstreams, nbytes, 0, w, nullptr)) return fail("bnflac_index_streams: out of device memory");
     bnf_stream_params p;
     memcpy(&p, sp, sizeof p);
     hipError_t e = bnf_launch_chain_streams(d_bytes, nbytes, (const bnf_stream_desc *)d_streams, nstreams, p, (uint32_t)C, w,
                                             d_frame_offsets, d_out_sample, (bnf_frame_info *)d_info, cap, d_stream_frames,
                                             d_stream_samples, d_status, s);
     return e == hipSuccess ? 0 : fail(std::string("bnflac_index_streams: ") + hipGetErrorString(e));
+}
+
+static_assert(sizeof(bnflac_index_cand) == sizeof(bnf_index_cand) && sizeof(bnf_index_cand) == 32, "index candidate layout");
+static_assert(sizeof(bnflac_resync_slot) == sizeof(bnf_resync_slot) && sizeof(bnf_resync_slot) == 16, "resync slot layout");
+static_assert(sizeof(bnflac_resync_rec) == sizeof(bnf_resync_rec) && sizeof(bnf_resync_rec) == 32, "resync record layout");
+static_assert(offsetof(bnflac_index_cand, succ) == 16 && offsetof(bnf_index_cand, succ) == 16 &&
+                  offsetof(bnflac_index_cand, flags) == 28 && offsetof(bnf_index_cand, flags) == 28,
+              "index candidate fields");
+static_assert(offsetof(bnflac_resync_rec, gap_samples) == 16 && offsetof(bnf_resync_rec, gap_samples) == 16,
+              "resync record: gap_samples @16");
+static_assert((uint32_t)BNFLAC_FRAME_GAP == (uint32_t)BNF_FL_GAP && (int)BNFLAC_RESYNC_LEADING == (int)BNF_RESYNC_LEADING &&
+                  (int)BNFLAC_RESYNC_RESYNCED == (int)BNF_RESYNC_RESYNCED,
+              "resync flag values");
+
+/* what both resync calls refuse about the blocksize */
+static const char *resync_refusal(const bnflac_stream_params *sp) {
+    if (!sp->has_stream_info) return "needs STREAMINFO (has_stream_info)";
+    if (sp->min_blocksize != sp->max_blocksize || sp->min_blocksize < 1) return "a fixed-blocksize stream only (min == max >= 1)";
+    return nullptr;
+}
+
+extern "C" BNFLAC_API int bnflac_index_streams_resync(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
+                                                      const bnflac_stream_desc *d_streams, uint32_t nstreams,
+                                                      const bnflac_stream_params *sp, uint32_t cand_cap,
+                                                      uint64_t *d_frame_offsets, uint64_t *d_out_sample,
+                                                      bnflac_frame_info *d_info, uint32_t cap, uint32_t *d_stream_frames,
+                                                      uint64_t *d_stream_samples, bnflac_resync_rec *d_resync,
+                                                      uint32_t *d_status, void *hs) {
+    if (check_args(ctx, d_bytes, nbytes, sp, "bnflac_index_streams_resync")) return -1;
+    if (const char *why = resync_refusal(sp)) return fail(std::string("bnflac_index_streams_resync: ") + why);
+    DevGuard dg(ctx->device); /* launches and scratch on the context's device */
+    if (!d_stream_frames || !d_status || (cap && !d_frame_offsets)) return fail("bnflac_index_streams_resync: null output");
+    if (nstreams && !d_streams) return fail("bnflac_index_streams_resync: null descriptor table");
+    if (nstreams >= (1u << 30)) return fail("bnflac_index_streams_resync: too many streams");
+    hipStream_t s = (hipStream_t)hs;
+    ctx->crcp_bytes = ctx->crcp_info = nullptr; /* the records this writes carry no CRC-16 hand-off */
+    ctx->rs_ct = nullptr;
+    if (!nstreams || !nbytes) { /* nothing to index: zeros */
+        hipError_t e = hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_stream_frames, 0, sizeof(uint32_t) * ((size_t)nstreams + 1), s);
+        if (e == hipSuccess && d_stream_samples)
+            e = hipMemsetAsync(d_stream_samples, 0, sizeof(uint64_t) * ((size_t)nstreams + 1), s);
+        if (e == hipSuccess && d_resync && nstreams) e = hipMemsetAsync(d_resync, 0, sizeof(bnf_resync_rec) * (size_t)nstreams, s);
+        return e == hipSuccess ? 0 : fail(std::string("bnflac_index_streams_resync: ") + hipGetErrorString(e));
+    }
+    const uint64_t C64 = cand_cap ? cand_cap : nbytes / 1024 + 4096;
+    if (C64 >= (1u << 30)) return fail("bnflac_index_streams_resync: cand_cap too large");
+    const uint32_t C = (uint32_t)C64;
+    bnf_ms_scratch w;
+    uint8_t *extra = nullptr;
+    if (!ms_scratch(ctx, C, nstreams, nbytes, (size_t)bnf_resync_scratch_bytes(C, nstreams), w, &extra))
+        return fail("bnflac_index_streams_resync: out of device memory");
+    const bnf_rs_scratch r = bnf_resync_carve(extra, C, nstreams);
+    bnf_stream_params p;
+    memcpy(&p, sp, sizeof p);
+    hipError_t e = bnf_launch_chain_streams_resync(d_bytes, nbytes, (const bnf_stream_desc *)d_streams, nstreams, p, C, w, r,
+                                                   d_frame_offsets, d_out_sample, (bnf_frame_info *)d_info, cap,
+                                                   d_stream_frames, d_stream_samples, (bnf_resync_rec *)d_resync, d_status, s);
+    if (e != hipSuccess) return fail(std::string("bnflac_index_streams_resync: ") + hipGetErrorString(e));
+    ctx->rs_ct = r.ct;
+    ctx->rs_ctl = w.ctl;
+    return 0;
+}
+
+extern "C" BNFLAC_API int bnflac_debug_index_candidates(bnflac_ctx *ctx, bnflac_index_cand *out, uint32_t cap,
+                                                        uint32_t *ncand) {
+    if (!ctx || !ncand || (cap && !out)) return fail("bnflac_debug_index_candidates: null argument");
+    if (!ctx->rs_ct) return fail("bnflac_debug_index_candidates: no resync call on this context since its scratch was reused");
+    DevGuard dg(ctx->device);
+    uint32_t ctl[BNF_MS_CTL_WORDS];
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctl, ctx->rs_ctl, sizeof ctl, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("bnflac_debug_index_candidates: HIP error");
+    *ncand = ctl[BNF_MS_N];
+    const uint32_t k = std::min(ctl[BNF_MS_N], cap);
+    if (k && hipMemcpy(out, ctx->rs_ct, sizeof(bnf_index_cand) * (size_t)k, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("bnflac_debug_index_candidates: HIP error");
+    return 0;
+}
+
+extern "C" BNFLAC_API int bnflac_resync_plan_host(const bnflac_index_cand *cands, uint32_t ncand,
+                                                  const bnflac_stream_desc *streams, uint32_t nstreams, uint32_t B,
+                                                  bnflac_resync_slot *slots, uint32_t cap, uint32_t *stream_frames,
+                                                  uint64_t *stream_samples, bnflac_resync_rec *resync, uint32_t status[4]) {
+    if (!stream_frames || !stream_samples || !status) return fail("bnflac_resync_plan_host: null output");
+    if ((ncand && !cands) || (nstreams && !streams)) return fail("bnflac_resync_plan_host: null table");
+    if (B < 1) return fail("bnflac_resync_plan_host: the blocksize must be at least 1");
+    if (ncand >= (1u << 30) || nstreams >= (1u << 30)) return fail("bnflac_resync_plan_host: table too large");
+    if (!bnf_resync_plan_host((const bnf_index_cand *)cands, ncand, (const bnf_stream_desc *)streams, nstreams, B,
+                              (bnf_resync_slot *)slots, cap, stream_frames, stream_samples, (bnf_resync_rec *)resync, status))
+        return fail("bnflac_resync_plan_host: out of memory");
+    return 0;
 }
 
 static_assert(sizeof(bnflac_stream_meta) == sizeof(bnf_stream_meta) && sizeof(bnf_stream_meta) == 64, "stream meta layout");

@@ -132,6 +132,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_select_windows", "bnflac_select_windows_host",
                  "bnflac_select_windows_shared", "bnflac_select_windows_shared_host",
                  "bnflac_window_health", "bnflac_window_health_host",
+                 "bnflac_index_streams_resync", "bnflac_resync_plan_host", "bnflac_debug_index_candidates",
                  "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
@@ -202,6 +203,14 @@ def load() -> ctypes.CDLL:
     L.bnflac_index_streams.restype = i
     L.bnflac_index_streams.argtypes = [p, p, ctypes.c_uint64, p, ctypes.c_uint32, p, ctypes.c_uint32, p, p, p,
                                        ctypes.c_uint32, p, p, p, p]
+    L.bnflac_index_streams_resync.restype = i
+    L.bnflac_index_streams_resync.argtypes = [p, p, ctypes.c_uint64, p, ctypes.c_uint32, p, ctypes.c_uint32, p, p, p,
+                                              ctypes.c_uint32, p, p, p, p, p]
+    L.bnflac_resync_plan_host.restype = i
+    L.bnflac_resync_plan_host.argtypes = [p, ctypes.c_uint32, p, ctypes.c_uint32, ctypes.c_uint32, p, ctypes.c_uint32, p, p,
+                                          p, p]
+    L.bnflac_debug_index_candidates.restype = i
+    L.bnflac_debug_index_candidates.argtypes = [p, p, ctypes.c_uint32, p]
     L.bnflac_reader_open.restype = i
     L.bnflac_reader_open.argtypes = [i, p, ctypes.c_uint64, i, ctypes.c_uint32, ctypes.POINTER(p)]
     L.bnflac_reader_params.restype = i
@@ -603,6 +612,57 @@ def window_health_host(sel_info: np.ndarray, sel_cap: int, windows: np.ndarray, 
     return health, status
 
 
+FRAME_GAP = 0x800  # FRAME_INFO flags of a placeholder record of index_streams_resync
+INDEX_CAND_BYTES, RESYNC_SLOT_BYTES, RESYNC_REC_BYTES = 32, 16, 32
+# bnflac_index_cand: one sync candidate after the indexer's first three steps; succ and stream -1 for none
+INDEX_CAND_DTYPE = np.dtype([("offset", "<u8"), ("number", "<u8"), ("succ", "<i4"), ("stream", "<i4"),
+                             ("blocksize", "<u4"), ("flags", "<u4")])
+CAND_VALID, CAND_SAMPLE_NUMBER = 1, 2  # INDEX_CAND flags
+# bnflac_resync_slot: one record position of resync_plan_host
+RESYNC_SLOT_DTYPE = np.dtype([("cand", "<u4"), ("gap", "<u4"), ("position", "<u8")])
+# bnflac_resync_rec: one stream's record of index_streams_resync
+RESYNC_REC_DTYPE = np.dtype([("flags", "<u4"), ("segments", "<u4"), ("gap_frames", "<u4"), ("reserved", "<u4"),
+                             ("gap_samples", "<u8"), ("base", "<u8")])
+assert (INDEX_CAND_DTYPE.itemsize, RESYNC_SLOT_DTYPE.itemsize, RESYNC_REC_DTYPE.itemsize) == \
+    (INDEX_CAND_BYTES, RESYNC_SLOT_BYTES, RESYNC_REC_BYTES)
+RESYNC_RESYNCED, RESYNC_CONTRADICTION, RESYNC_HEAD, RESYNC_LEADING = 1, 2, 4, 8  # RESYNC_REC flags
+
+
+def index_cand_array(raw: np.ndarray) -> np.ndarray:
+    """View a uint8 buffer of candidate records as a structured array."""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=INDEX_CAND_DTYPE)
+
+
+def resync_slot_array(raw: np.ndarray) -> np.ndarray:
+    """View a uint8 buffer of resync_plan_host slots as a structured array."""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=RESYNC_SLOT_DTYPE)
+
+
+def resync_array(raw: np.ndarray) -> np.ndarray:
+    """View a uint8 buffer of index_streams_resync's per-stream records as a structured array."""
+    return np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=RESYNC_REC_DTYPE)
+
+
+def resync_plan_host(cands: np.ndarray, streams: np.ndarray, blocksize: int, cap: int):
+    """The rule of index_streams_resync over host tables (bnflac_resync_plan_host, no GPU).  cands: an
+    INDEX_CAND_DTYPE table (BatchDecoder.index_candidates gives the device's), streams: the
+    STREAM_DESC_DTYPE table, blocksize: STREAMINFO's fixed blocksize, cap: the slots to provide.
+    -> (slots[min(records, cap)] in RESYNC_SLOT_DTYPE, stream_frames uint32[n + 1],
+        stream_samples uint64[n + 1], resync[n] in RESYNC_REC_DTYPE, status uint32[4])"""
+    c = np.ascontiguousarray(cands, dtype=INDEX_CAND_DTYPE)
+    sd = np.ascontiguousarray(streams, dtype=STREAM_DESC_DTYPE)
+    n = len(sd)
+    slots = np.zeros(max(cap, 1), dtype=RESYNC_SLOT_DTYPE)
+    sf, ss = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint64)
+    rec, status = np.zeros(max(n, 1), dtype=RESYNC_REC_DTYPE), np.zeros(4, np.uint32)
+    vp = lambda a: (a if a.size else np.zeros(1, a.dtype)).ctypes.data_as(ctypes.c_void_p)
+    rc = load().bnflac_resync_plan_host(vp(c), len(c), vp(sd), n, blocksize, vp(slots), cap, vp(sf), vp(ss), vp(rec),
+                                        vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return slots[: min(int(status[2]), cap)], sf, ss, rec[:n], status
+
+
 def stream_table(streams, nbytes: int) -> np.ndarray:
     """The descriptor table of index_streams from [(begin, end, first_offset, total_samples)],
     checked as the library checks it (its status bit 2): ValueError for a range that is
@@ -695,12 +755,13 @@ class Corpus:
     same stream, or the caller's events)."""
 
     def __init__(self, d_bytes, nbytes, sp, nstreams, cap, d_offsets, d_info, d_stream_frames, d_stream_samples,
-                 scan_status, index_status, d_streams=None):
+                 scan_status, index_status, d_streams=None, d_resync=None):
         self.d_bytes, self.nbytes, self.sp, self.nstreams, self.cap = d_bytes, nbytes, sp, nstreams, cap
         self.d_offsets, self.d_info = d_offsets, d_info
         self.d_stream_frames, self.d_stream_samples = d_stream_frames, d_stream_samples
         self.scan_status, self.index_status = scan_status, index_status  # device int32[4] each, not synchronised
         self.d_streams = d_streams  # scan_streams' descriptor table, int64[nstreams * 4], or None
+        self.d_resync = d_resync  # index_streams_resync's records, uint8[nstreams * 32], or None (no resync)
 
     def missing_samples(self):
         """Per stream, the sample frames STREAMINFO promises and the index lacks (a damaged stream's
@@ -777,6 +838,31 @@ class BatchDecoder:
         -> (d_offsets int64[cap], d_out_sample int64[cap], d_info uint8[cap*128],
             d_stream_frames int32[n+1], d_stream_samples int64[n+1], d_status int32[4]),
         all on the device and not synchronised: the caller does that, as for decode_parsed."""
+        return self._index_streams(d_bytes, nbytes, streams, sp, cap, cand_cap, stream, False)
+
+    def index_streams_resync(self, d_bytes, nbytes: int, streams, sp: StreamParams, cap: int, cand_cap: int = 0,
+                             stream=None):
+        """index_streams with resynchronisation (bnflac_index_streams_resync): a fixed-blocksize stream's
+        chain goes on behind its damage, placeholder records (flags FRAME_GAP) hold the lost samples,
+        and every later call takes the tables unchanged.  ValueError unless sp has STREAMINFO with
+        min_blocksize == max_blocksize >= 1.
+        -> index_streams' tuple plus d_resync uint8[n * 32] (resync_array), not synchronised."""
+        if not sp.has_stream_info or sp.min_blocksize != sp.max_blocksize or sp.min_blocksize < 1:
+            raise ValueError("index_streams_resync needs a fixed-blocksize stream: STREAMINFO with min_blocksize == max_blocksize")
+        return self._index_streams(d_bytes, nbytes, streams, sp, cap, cand_cap, stream, True)
+
+    def index_candidates(self) -> np.ndarray:
+        """Debug: the candidate table of the last index_streams_resync call, synchronously
+        (bnflac_debug_index_candidates) -> INDEX_CAND_DTYPE[ncand]."""
+        n = ctypes.c_uint32(0)
+        if self.L.bnflac_debug_index_candidates(self.ctx, None, 0, ctypes.byref(n)) != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        out = np.zeros(max(n.value, 1), dtype=INDEX_CAND_DTYPE)
+        if self.L.bnflac_debug_index_candidates(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)) != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        return out[: n.value]
+
+    def _index_streams(self, d_bytes, nbytes, streams, sp, cap, cand_cap, stream, resync):
         import torch
         dev = d_bytes.device
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -795,14 +881,19 @@ class BatchDecoder:
             d_sf = torch.zeros(n + 1, dtype=torch.int32, device=dev)
             d_ss = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             d_status = torch.zeros(4, dtype=torch.int32, device=dev)
-        rc = self.L.bnflac_index_streams(self.ctx, ctypes.c_void_p(d_bytes.data_ptr()), nbytes,
-                                         ctypes.c_void_p(d_tab.data_ptr()) if n else None, n, ctypes.byref(sp), cand_cap,
-                                         ctypes.c_void_p(d_offs.data_ptr()), ctypes.c_void_p(d_os.data_ptr()),
-                                         ctypes.c_void_p(d_info.data_ptr()), cap, ctypes.c_void_p(d_sf.data_ptr()),
-                                         ctypes.c_void_p(d_ss.data_ptr()), ctypes.c_void_p(d_status.data_ptr()),
-                                         self._stream(s))
+            d_rs = torch.zeros(max(n, 1) * RESYNC_REC_BYTES, dtype=torch.uint8, device=dev) if resync else None
+        head = (self.ctx, ctypes.c_void_p(d_bytes.data_ptr()), nbytes, ctypes.c_void_p(d_tab.data_ptr()) if n else None, n,
+                ctypes.byref(sp), cand_cap, ctypes.c_void_p(d_offs.data_ptr()), ctypes.c_void_p(d_os.data_ptr()),
+                ctypes.c_void_p(d_info.data_ptr()), cap, ctypes.c_void_p(d_sf.data_ptr()), ctypes.c_void_p(d_ss.data_ptr()))
+        tail = (ctypes.c_void_p(d_status.data_ptr()), self._stream(s))
+        if resync:
+            rc = self.L.bnflac_index_streams_resync(*head, ctypes.c_void_p(d_rs.data_ptr()), *tail)
+        else:
+            rc = self.L.bnflac_index_streams(*head, *tail)
         if rc != 0:
             raise RuntimeError(self.L.bnflac_last_error().decode())
+        if resync:
+            return d_offs, d_os, d_info, d_sf, d_ss, d_status, d_rs[: n * RESYNC_REC_BYTES]
         return d_offs, d_os, d_info, d_sf, d_ss, d_status
 
     @staticmethod
@@ -1224,20 +1315,31 @@ class BatchDecoder:
         return planes, status
 
     def index_corpus(self, d_bytes, nbytes: int, ranges_bytes, sp: StreamParams, cap: Optional[int] = None,
-                     cand_cap: int = 0, stream=None) -> Corpus:
+                     cand_cap: int = 0, stream=None, resync: bool = False) -> Corpus:
         """scan_streams -> index_streams over the .flac files of a buffer, once, for any number of
         decode_crops / decode_crops_f32 calls.  Arguments as for decode_windows (cap defaults to
         nbytes // 16 + 16); nothing is synchronised or read back.  The caller keeps d_bytes alive and
         unchanged as long as the Corpus is used, and orders that use after this call (the same
-        stream, or events)."""
+        stream, or events).
+        resync: index_streams_resync in index_streams' place (fixed-blocksize streams; ValueError when
+        sp.min_blocksize != sp.max_blocksize): a damaged stream loses its damaged frames only, whose
+        samples come back as zeros in a crop that window_health calls DAMAGED; Corpus.d_resync holds
+        the per-stream records (None without resync)."""
         import torch
+        if resync and sp.min_blocksize != sp.max_blocksize:
+            raise ValueError("resync needs a fixed-blocksize stream: sp.min_blocksize != sp.max_blocksize")
         s = stream if stream is not None else torch.cuda.current_stream()
         n = ranges_bytes.numel() // 4 if isinstance(ranges_bytes, torch.Tensor) else len(ranges_bytes)
         cap = nbytes // 16 + 16 if cap is None else cap
         d_tab, _, _, st_scan = self.scan_streams(d_bytes, nbytes, ranges_bytes, expect=sp, stream=s)
-        d_offs, _, d_info, d_sf, d_ss, st_index = self.index_streams(d_bytes, nbytes, d_tab, sp, cap, cand_cap=cand_cap,
-                                                                     stream=s)
-        return Corpus(d_bytes, nbytes, sp, n, cap, d_offs, d_info, d_sf, d_ss, st_scan, st_index, d_tab)
+        d_rs = None
+        if resync:
+            d_offs, _, d_info, d_sf, d_ss, st_index, d_rs = self.index_streams_resync(d_bytes, nbytes, d_tab, sp, cap,
+                                                                                      cand_cap=cand_cap, stream=s)
+        else:
+            d_offs, _, d_info, d_sf, d_ss, st_index = self.index_streams(d_bytes, nbytes, d_tab, sp, cap, cand_cap=cand_cap,
+                                                                         stream=s)
+        return Corpus(d_bytes, nbytes, sp, n, cap, d_offs, d_info, d_sf, d_ss, st_scan, st_index, d_tab, d_rs)
 
     def _decode_crop_selection(self, corpus: Corpus, requests, nsamples, fmt, s, shared=False, max_frames=None,
                                max_samples=None, health=False):

@@ -23,6 +23,10 @@
  * the same requests and selects every frame once, the windows pointing into one shared compact PCM.
  * After the decode of any of these selections, bnflac_window_health says per window how much of it lies
  * in frames that failed to decode or failed their CRC, and how much of the request the index lacks.
+ * bnflac_index_streams ends a stream's frame chain at its first damaged frame.  For fixed-blocksize
+ * streams bnflac_index_streams_resync takes its place and goes on at the next frame start that its
+ * CRC-16 verifies, with placeholder records for the samples in between, so that only the damaged
+ * frames are lost and every later call works on its tables unchanged.
  *
  * Only plain C types cross this boundary (no torch, no HIP types: a HIP stream is
  * passed as void*).
@@ -156,7 +160,8 @@ BNFLAC_API int bnflac_index_frames(bnflac_ctx *ctx, const uint8_t *d_bytes, uint
  * rule).  Writes d_frame_offsets, d_out_sample (running sample count; may be NULL) and,
  * when d_info != NULL, the parsed records ready for bnflac_decode_parsed.  *d_nframes
  * (device) = chain length (only cap entries are written).  A damaged stream ends the
- * chain at the damage; the libFLAC stream API handles resync.  Synchronises hip_stream
+ * chain at the damage; the libFLAC stream API handles resync, and so does
+ * bnflac_index_streams_resync for the streams of a batch.  Synchronises hip_stream
  * once (candidate count); otherwise asynchronous. */
 BNFLAC_API int bnflac_index_stream(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes, uint64_t first_offset,
                                    const bnflac_stream_params *sp, uint64_t *d_frame_offsets, uint64_t *d_out_sample,
@@ -263,6 +268,123 @@ BNFLAC_API int bnflac_index_streams(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
                                     uint32_t *d_stream_frames, uint64_t *d_stream_samples, uint32_t *d_status,
                                     void *hip_stream);
 
+/* bnflac_frame_info.flags of a placeholder record of bnflac_index_streams_resync. */
+#define BNFLAC_FRAME_GAP 0x800u
+
+/* Per-stream result record of bnflac_index_streams_resync (32 bytes, 8-byte aligned), device-resident. */
+typedef struct {
+    uint32_t flags;       /* BNFLAC_RESYNC_* */
+    uint32_t segments;    /* runs of CRC-linked frames kept: 0 for a stream without records, 1 for an intact one */
+    uint32_t gap_frames;  /* placeholder records kept, saturating */
+    uint32_t reserved;    /* 0 */
+    uint64_t gap_samples; /* their samples: placeholders * blocksize */
+    uint64_t base;        /* the stream position that is sample 0 of the stream's records */
+} bnflac_resync_rec;
+enum {
+    BNFLAC_RESYNC_RESYNCED = 1,      /* the chain went on past at least one break */
+    BNFLAC_RESYNC_CONTRADICTION = 2, /* it ended at a frame start whose number does not fit the samples before it */
+    BNFLAC_RESYNC_HEAD = 4,          /* the first frame's number is no multiple of the blocksize or past the total: no records */
+    BNFLAC_RESYNC_LEADING = 8        /* placeholders stand in front of the first frame */
+};
+
+/* bnflac_index_streams with resynchronisation, for fixed-blocksize streams: sp must have
+ * has_stream_info and min_blocksize == max_blocksize = B >= 1, else the call returns a negative
+ * value and launches nothing.  Arguments, tables, cand_cap, cap and the zero cases are
+ * bnflac_index_streams'; d_resync (may be NULL) gets one record per stream.
+ * With P = number * B for a header that codes a frame number, else the coded sample number, a
+ * frame is linked to its CRC-16 successor (bnflac_index_streams' successor) when that frame's P
+ * is this frame's P plus its blocksize.  The second condition is what this call adds to a link:
+ * the CRC-16 of a run of zero bytes is zero, so a frame in front of zeroed frames closes at the
+ * next surviving frame start too, and only the header numbers tell that the frames in between are
+ * gone.  In an intact stream every successor is linked.
+ * Where a frame has no linked successor -- there bnflac_index_streams ends the stream's chain, or
+ * runs over a zeroed hole -- this call keeps that frame and goes on at the next frame start of the
+ * stream that is verified: a valid candidate at or after first_offset, of blocksize B, with a
+ * linked successor of its own, whose header number puts it on the stream's blocksize grid (below
+ * total_samples when that is known).  With base = 0 when the stream's total_samples is known, else
+ * the P of the stream's first frame (a stream of unknown length is rebased to its first frame, as
+ * bnflac_index_streams does):
+ *   - the first frame stands at P - base, with (P - base) / B placeholders in front of it
+ *     (BNFLAC_RESYNC_LEADING).  When total_samples is known and P is no multiple of B or not below
+ *     it, the stream gets no records (BNFLAC_RESYNC_HEAD);
+ *   - inside a run of linked frames every frame stands at the end of the one before it, as in
+ *     bnflac_index_streams;
+ *   - after a break at stream position E (the end of the last frame kept), the next verified start
+ *     stands at L = its P - base.  L < E, or L - E no multiple of B, ends the stream's chain before
+ *     that start (BNFLAC_RESYNC_CONTRADICTION; later starts are not tried).  Otherwise (L - E) / B
+ *     placeholders stand at E, E + B, ... and the chain goes on (BNFLAC_RESYNC_RESYNCED);
+ *   - with total_samples known, the first frame at or past it ends the chain: it and everything
+ *     after it are dropped, as in bnflac_index_streams, and nothing behind it sets a flag.  No
+ *     placeholders follow the last frame kept.
+ * A stream's records therefore tile [0, T), T = d_stream_samples[s + 1] - d_stream_samples[s], in
+ * position order, which is all that bnflac_select_ranges, bnflac_select_windows[_shared],
+ * bnflac_decode_parsed, both gathers, bnflac_md5_streams and bnflac_window_health rely on.  A
+ * frame's record is the parsed record with out_sample = d_stream_samples[s] + its position.  A
+ * placeholder is a record of zeros apart from status 1 with err 0 (lost sync), cached -1,
+ * blocksize B, sample_rate, channels and bps of sp, number = position / B, out_sample,
+ * sub_start[0] = 1 (so the decode zero-fills its range like that of any frame that failed after
+ * its header) and flags = BNFLAC_FRAME_GAP; its frame_off and its d_frame_offsets entry are the
+ * offset of the frame that follows the gap.  Placeholders are made for d_info ->
+ * bnflac_decode_parsed: bnflac_parse_frames / bnflac_decode_frames over these offsets would parse
+ * the following frame a second time in the placeholder's place.
+ * Record counts are taken in 64 bits; the tables and the status hold min(count, 2^32 - 1), and only
+ * positions below cap are written, however long a gap is.
+ * d_status: [0] bits 0-2 as for bnflac_index_streams, bit 3 some stream has placeholders or
+ * resynced, bit 4 some stream has CONTRADICTION or HEAD; [1] candidates found; [2] records in total;
+ * [3] placeholders in total.
+ * For a stream whose every successor is linked (its header numbers run on, as an encoder writes
+ * them) and whose first frame has P == base, every output is byte for byte what
+ * bnflac_index_streams writes.
+ * Known limits: a frame between two damaged neighbours has no verified successor and is not
+ * resumed at (libFLAC delivers it; here the chain goes on behind it, or ends, and
+ * bnflac_window_health reports the rest as missing).  A contradiction ends the chain instead of
+ * trying the next start.  Variable-blocksize streams are refused.  The CRC-16 hand-off of an
+ * earlier bnflac_parse_frames is dropped, as by bnflac_index_streams.  Asynchronous on hip_stream,
+ * no host synchronisation. */
+BNFLAC_API int bnflac_index_streams_resync(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
+                                           const bnflac_stream_desc *d_streams, uint32_t nstreams,
+                                           const bnflac_stream_params *sp, uint32_t cand_cap, uint64_t *d_frame_offsets,
+                                           uint64_t *d_out_sample, bnflac_frame_info *d_info, uint32_t cap,
+                                           uint32_t *d_stream_frames, uint64_t *d_stream_samples,
+                                           bnflac_resync_rec *d_resync, uint32_t *d_status, void *hip_stream);
+
+/* One sync candidate as the indexer sees it after its first three steps (32 bytes). */
+typedef struct {
+    uint64_t offset;    /* of the 0xFF sync byte */
+    uint64_t number;    /* the header's frame or sample number (0 unless valid) */
+    int32_t succ;       /* the first later valid candidate of the stream at which this one's CRC-16 closes, -1 none
+                           (as bnflac_index_streams takes it: the header numbers are not compared here) */
+    int32_t stream;     /* the stream whose range holds it, -1 none */
+    uint32_t blocksize; /* 0 unless valid */
+    uint32_t flags;     /* bit 0 valid: parsed as a frame start inside its stream; bit 1 the number is a sample number */
+} bnflac_index_cand;
+
+/* One record position of bnflac_resync_plan_host (16 bytes). */
+typedef struct {
+    uint32_t cand;     /* the frame's candidate; for a placeholder, the frame that follows the gap */
+    uint32_t gap;      /* 1 for a placeholder, else 0 */
+    uint64_t position; /* first sample of the record inside its stream */
+} bnflac_resync_slot;
+
+/* The rule of bnflac_index_streams_resync as a plain walk over host tables (no GPU; the code of
+ * csrc/bnf_resync.h that the kernels run).  The candidates of a stream are the entries with that
+ * stream id, in table order; a succ that does not point forward inside the same stream counts as
+ * none, as does one whose header numbers do not run on.  slots (cap entries; may be NULL) gets one entry per record position below cap,
+ * stream_frames and stream_samples (nstreams + 1 entries each) the prefixes, resync (may be NULL)
+ * the per-stream records, status the four words (bits 0 and 2 of word 0 are the device call's
+ * own and stay 0; word 1 is ncand).  0, or a negative value with nothing written for B == 0, a
+ * null table or output, or 2^30 or more entries. */
+BNFLAC_API int bnflac_resync_plan_host(const bnflac_index_cand *cands, uint32_t ncand, const bnflac_stream_desc *streams,
+                                       uint32_t nstreams, uint32_t B, bnflac_resync_slot *slots, uint32_t cap,
+                                       uint32_t *stream_frames, uint64_t *stream_samples, bnflac_resync_rec *resync,
+                                       uint32_t status[4]);
+
+/* Debug: the candidate table of ctx's last bnflac_index_streams_resync call, synchronously: *ncand
+ * candidates in all (0 when the table was malformed or cand_cap overflowed), min(*ncand, cap) of
+ * them in out.  0, or -1 when the context holds none (no such call, or bnflac_index_streams has
+ * reused the scratch since). */
+BNFLAC_API int bnflac_debug_index_candidates(bnflac_ctx *ctx, bnflac_index_cand *out, uint32_t cap, uint32_t *ncand);
+
 /* Decode nframes frames starting at d_frame_offsets (byte offsets into d_bytes).
  * Output position of each frame: d_out_sample[i] if non-NULL, else the header's
  * sample number (frame number x STREAMINFO blocksize for fixed-blocksize streams) minus
@@ -294,7 +416,7 @@ BNFLAC_API int bnflac_decode_frames(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
  * decorrelation, packing and CRC-16 (k_decode).  decode must follow parse on the same
  * stream with the same arguments.  The parse also does part of the CRC-16 work of 2-channel
  * frames and hands it to the next bnflac_decode_parsed call on the same ctx with the same
- * d_bytes, nbytes, d_info and nframes (used once; bnflac_index_stream and bnflac_index_streams drop it): the frame
+ * d_bytes, nbytes, d_info and nframes (used once; bnflac_index_stream, bnflac_index_streams and bnflac_index_streams_resync drop it): the frame
  * bytes must not change between the two calls (bnflac_debug_set_crc_mode). */
 BNFLAC_API int bnflac_parse_frames(bnflac_ctx *ctx, const uint8_t *d_bytes, uint64_t nbytes,
                                    const uint64_t *d_frame_offsets, uint32_t nframes,
