@@ -4464,6 +4464,10 @@ struct SideQ {
 };
 static std::mutex g_side_mu;
 static std::atomic<uint64_t> g_seg_launches{0}; /* k_decode_seg launches (bnf_decode_seg_launches) */
+/* what the last bnf_launch_decode and bnf_launch_parse of the process chose (bnf_last_route; BNF_ROUTE_*) */
+static std::atomic<uint32_t> g_route[BNF_ROUTE_WORDS];
+static void route_set(int i, uint32_t v) { g_route[i].store(v, std::memory_order_relaxed); }
+static void route_count(int i) { route_set(i, g_route[i].load(std::memory_order_relaxed) + 1u); } /* no locked op on the launch path */
 static SideQ g_side[64];
 static int decode_fork_mode() { /* 0 serial; 1 fork after k_decode_st; 2 fork before it (default) */
     static const int m = [] {
@@ -4569,6 +4573,9 @@ extern "C" {
 int bnf_crc_mode() { return crc_mode(); }
 void bnf_set_crc_mode(int mode) { g_crc_mode.store(mode < 0 ? -1 : std::min(mode, 3), std::memory_order_relaxed); } /* -1: env */
 uint64_t bnf_decode_seg_launches() { return g_seg_launches.load(std::memory_order_relaxed); }
+void bnf_last_route(uint32_t *out) {
+    for (int i = 0; i < BNF_ROUTE_WORDS; i++) out[i] = g_route[i].load(std::memory_order_relaxed);
+}
 void bnf_set_decode_sys(int mode) { g_decode_sys.store(mode < 0 ? 2 : (mode ? 1 : 0), std::memory_order_relaxed); } /* -1: auto */
 void bnf_set_parse_wave(int mode) { g_parse_wave.store(mode < 0 ? 2 : (mode ? 1 : 0), std::memory_order_relaxed); } /* -1: auto */
 hipError_t bnf_parse_wave_stats(uint64_t *out8, int reset) { /* debug counters of k_parse_wave (BNFLAC_PW_STATS=1) */
@@ -4589,6 +4596,9 @@ hipError_t bnf_launch_parse(const uint32_t *words, uint64_t nbytes, const uint64
         static const int seg = [] { const char *e = getenv("BNFLAC_PW_SEG"); return e ? atoi(e) : 0; }();
         hipLaunchKernelGGL(k_parse_wave, dim3(nframes), dim3(64), 0, s, words, nbytes, frame_offs, nframes, sp,
                            out_sample_in, base_sample, info, pws, seg);
+        route_set(BNF_ROUTE_PARSE, BNF_RT_PARSE_WAVE);
+        route_set(BNF_ROUTE_CM, 0u);
+        route_count(BNF_ROUTE_NPARSE);
         return hipGetLastError();
     }
     /* (Round 5: k_parse's occupancy is 5 waves per SIMD, LDS-bound; 4 or 3, by padding the LDS
@@ -4608,6 +4618,7 @@ hipError_t bnf_launch_parse(const uint32_t *words, uint64_t nbytes, const uint64
      * frames, whose side instances then outlast k_decode_st (C4: k_parse +0.6 ms for no
      * decode gain) */
     int cm = crcp ? crc_mode() : 0;
+    uint32_t rt = 0;
     if (cm == 3 && sp.bps <= 16u) {
         std::lock_guard<std::mutex> lk(g_side_mu);
         const SideQ *sq = side_queue();
@@ -4615,9 +4626,16 @@ hipError_t bnf_launch_parse(const uint32_t *words, uint64_t nbytes, const uint64
             const uint32_t w16 = __atomic_load_n(&sq->cls[0], __ATOMIC_RELAXED), w32 = __atomic_load_n(&sq->cls[1], __ATOMIC_RELAXED),
                            n = __atomic_load_n(&sq->cls[2], __ATOMIC_RELAXED);
             if (w16 != ~0u && w32 != ~0u && n != ~0u && 4ull * ((uint64_t)w16 + w32) >= n && n) cm = 0;
+            rt = BNF_RT_PARSE_HIST;
+            route_set(BNF_ROUTE_PARSE_HIST, w16);
+            route_set(BNF_ROUTE_PARSE_HIST + 1, w32);
+            route_set(BNF_ROUTE_PARSE_HIST + 2, n);
         }
     }
     if (cm == 3) cm = 1;
+    route_set(BNF_ROUTE_PARSE, rt);
+    route_set(BNF_ROUTE_CM, (uint32_t)cm);
+    route_count(BNF_ROUTE_NPARSE);
     if (handed) *handed = cm != 0;
     const dim3 g((nframes + 63) / 64);
     if (cm == 2)
@@ -4657,6 +4675,8 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
             e = bnf_launch_decode_sys(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, list, mode, s);
         if (e == hipSuccess)
             e = bnf_launch_decode_list(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, list, mode, s);
+        route_set(BNF_ROUTE_DECODE, BNF_RT_SYS);
+        route_count(BNF_ROUTE_NDECODE);
         return e;
     }
     /* the class segments of the decode order (bucket ends), for the W16 / W32 grids */
@@ -4686,10 +4706,14 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
     }
     /* W16 / W32 grids: the full-size side grids, or -- when the previous decode order on this
      * device had neither class (read from host memory one batch behind, no sync; a stale or
-     * wrong guess only costs time) -- k_decode_seg over both classes after k_decode<8> */
+     * wrong guess only costs time) -- k_decode_seg over both classes after k_decode<8>.
+     * All four words are read here, before this batch's own order is enqueued (it rewrites
+     * them), so after a synchronize the choice below is a function of the previous batch alone */
     uint32_t *cls = (sq && seg_on && order) ? sq->cls : nullptr;
-    const bool seg_only = cls && __atomic_load_n(&cls[0], __ATOMIC_RELAXED) == 0u &&
-                          __atomic_load_n(&cls[1], __ATOMIC_RELAXED) == 0u;
+    uint32_t hist[4] = {0u, 0u, 0u, 0u};
+    if (cls)
+        for (int i = 0; i < 4; i++) hist[i] = __atomic_load_n(&cls[i], __ATOMIC_RELAXED);
+    const bool seg_only = cls && hist[0] == 0u && hist[1] == 0u;
     const uint32_t *perm = nullptr;
     hipError_t e = hipSuccess;
     if (order) e = launch_order<0>(info, nullptr, 0, nullptr, nframes, order, &perm, s, cls);
@@ -4703,8 +4727,11 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
      * on a third side stream beside k_decode_st, and after k_decode_st only its hand-backs.
      * One launch after k_decode_st put both on the stream's critical path (C4 at 32 copies:
      * k_decode_st 11.7 ms, then k_decode<8> 6.3 ms, while the W16 / W32 grids ended at 10.9). */
-    const bool w8split = sq && seg && cls && __atomic_load_n(&cls[3], __ATOMIC_RELAXED) != 0u &&
-                         !(bnf_ablate_flags() & BNF_ABLATE_NO_W8SPLIT); /* open: the split stays on under BNF_ABLATE_NO_ST */
+    /* Not under BNF_ABLATE_NO_ST: k_decode_st is then not launched and no frame counts as a
+     * stereo fast-path frame, so the STREDO launch would take nothing and the NOST launch only
+     * the blocks of class 1; the single launch takes every class-0 and class-1 frame. */
+    const bool w8split = sq && seg && cls && hist[3] != 0u &&
+                         !(bnf_ablate_flags() & (BNF_ABLATE_NO_W8SPLIT | BNF_ABLATE_NO_ST));
     const int nside = w8split ? 3 : 2;
     auto fork = [&]() -> hipError_t {
         hipError_t r = hipEventRecord(sq->fork, s);
@@ -4747,6 +4774,10 @@ hipError_t bnf_launch_decode(const uint32_t *words, uint64_t nbytes, uint32_t nf
         if (e == hipSuccess) e = bnf_launch_decode_w16(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
         if (e == hipSuccess) e = bnf_launch_decode_w32(words, nbytes, nframes, sp, chn_lanes, fmt, out, out_bytes, info, perm, mode, seg, s);
     }
+    route_set(BNF_ROUTE_DECODE, (sq ? (fm == 2 ? BNF_RT_FORK_BEFORE : BNF_RT_FORK_AFTER) : seg_only ? BNF_RT_SEG_ONLY : BNF_RT_SERIAL) |
+                                    (w8split ? BNF_RT_W8SPLIT : 0u) | (sw ? BNF_RT_SW : 0u) | (cls ? BNF_RT_HIST : 0u));
+    for (int i = 0; i < 4; i++) route_set(BNF_ROUTE_HIST + i, hist[i]);
+    route_count(BNF_ROUTE_NDECODE);
     return e;
 }
 

@@ -186,6 +186,29 @@ void bnf_set_crc_mode(int mode);    /* -1: env */
 void bnf_set_decode_sys(int mode);  /* -1: auto */
 void bnf_set_parse_wave(int mode);  /* -1: auto */
 uint64_t bnf_decode_seg_launches(void);
+/* The route of the process's last bnf_launch_decode and bnf_launch_parse (plain host atomics the
+ * launchers write; include/bnflac.h, bnflac_debug_last_route, has the same layout). */
+enum {
+    BNF_ROUTE_DECODE = 0,     /* BNF_RT_* of the decode */
+    BNF_ROUTE_HIST = 1,       /* 4 words: SideQ::cls as the decode read it (with BNF_RT_HIST) */
+    BNF_ROUTE_NDECODE = 5,    /* bnf_launch_decode calls that launched something */
+    BNF_ROUTE_PARSE = 6,      /* BNF_RT_PARSE_* */
+    BNF_ROUTE_CM = 7,         /* the hand-off mode launched: 0, 1 or 2 */
+    BNF_ROUTE_NPARSE = 8,     /* bnf_launch_parse calls that launched something */
+    BNF_ROUTE_PARSE_HIST = 9, /* 3 words: cls[0..2] as the parse read them (with BNF_RT_PARSE_HIST) */
+    BNF_ROUTE_WORDS = 12
+};
+#define BNF_RT_SYS 1u         /* k_decode_sys, then k_decode_list */
+#define BNF_RT_FORK_BEFORE 2u /* side grids forked before k_decode_st */
+#define BNF_RT_FORK_AFTER 4u  /* side grids forked after k_decode_st */
+#define BNF_RT_SERIAL 8u      /* the W16 / W32 grids on the caller's stream */
+#define BNF_RT_SEG_ONLY 16u   /* k_decode_seg instead of the W16 / W32 grids */
+#define BNF_RT_W8SPLIT 32u    /* k_decode<8> as two launches */
+#define BNF_RT_SW 64u         /* k_decode_sw ran first */
+#define BNF_RT_HIST 128u      /* the decode read the history words */
+#define BNF_RT_PARSE_WAVE 1u  /* k_parse_wave ran (no hand-off) */
+#define BNF_RT_PARSE_HIST 2u  /* the parse consulted the history for its hand-off mode */
+void bnf_last_route(uint32_t *out); /* BNF_ROUTE_WORDS words */
 hipError_t bnf_parse_wave_stats(uint64_t *out8, int reset);
 /* words: 16-byte aligned; the allocation must cover round_up(nbytes, 16) bytes.
  * order: nullptr, or 256 + nframes words of device scratch for the frame order (k_order_*);

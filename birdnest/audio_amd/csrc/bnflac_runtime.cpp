@@ -131,6 +131,11 @@ extern "C" BNFLAC_API void bnflac_debug_set_decode_sys(int mode) { bnf_set_decod
  * 3 the prefix where it pays (bnf_launch_parse) */
 extern "C" BNFLAC_API void bnflac_debug_set_crc_mode(int mode) { bnf_set_crc_mode(mode); }
 extern "C" BNFLAC_API uint64_t bnflac_debug_decode_seg_launches(void) { return bnf_decode_seg_launches(); }
+/* which kernels and streams the process's last decode and parse launches chose, and the history
+ * words they read (include/bnflac.h; 12 words) */
+extern "C" BNFLAC_API void bnflac_debug_last_route(uint32_t *out12) {
+    if (out12) bnf_last_route(out12);
+}
 /* k_parse_wave's debug counters (collected when BNFLAC_PW_STATS is set): passes, splice rounds,
  * serial fallbacks, partitions, frames, wave-cycles in scans.  out8: 8 values. */
 extern "C" BNFLAC_API int bnflac_debug_parse_wave_stats(uint64_t *out8, int reset) {

@@ -125,7 +125,8 @@ DECODER_SYMBOLS = [
 BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error", "bnflac_device_count",
                  "bnflac_index_frames", "bnflac_decode_frames", "bnflac_parse_frames", "bnflac_decode_parsed",
                  "bnflac_out_stride", "bnflac_debug_set_ablate", "bnflac_debug_stats", "bnflac_debug_set_parse_wave", "bnflac_debug_parse_wave_stats",
-                 "bnflac_debug_set_decode_sys", "bnflac_debug_decode_seg_launches", "bnflac_md5_interleaved32", "bnflac_index_stream",
+                 "bnflac_debug_set_decode_sys", "bnflac_debug_decode_seg_launches", "bnflac_debug_last_route",
+                 "bnflac_md5_interleaved32", "bnflac_index_stream",
                  "bnflac_index_streams", "bnflac_md5_layout", "bnflac_md5_streams",
                  "bnflac_scan_streams", "bnflac_scan_stream_host",
                  "bnflac_select_ranges", "bnflac_select_ranges_host", "bnflac_gather_ranges",
@@ -189,6 +190,7 @@ def load() -> ctypes.CDLL:
     L.bnflac_debug_crc_handoff.restype = i
     L.bnflac_debug_crc_handoff.argtypes = [p, p, ctypes.c_uint32]
     L.bnflac_debug_decode_seg_launches.restype, L.bnflac_debug_decode_seg_launches.argtypes = ctypes.c_uint64, []
+    L.bnflac_debug_last_route.restype, L.bnflac_debug_last_route.argtypes = None, [ctypes.POINTER(ctypes.c_uint32)]
     L.bnflac_debug_parse_wave_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     L.bnflac_debug_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     L.bnflac_debug_stats.restype = ctypes.c_int
@@ -685,6 +687,26 @@ def stream_table(streams, nbytes: int) -> np.ndarray:
 
 def out_stride(fmt: int, sp: StreamParams) -> int:
     return int(load().bnflac_out_stride(fmt, ctypes.byref(sp)))
+
+
+# bnflac_debug_last_route, word 0 (the decode) and word 6 (the parse)
+RT_SYS, RT_FORK_BEFORE, RT_FORK_AFTER, RT_SERIAL, RT_SEG_ONLY, RT_W8SPLIT, RT_SW, RT_HIST = 1, 2, 4, 8, 16, 32, 64, 128
+RT_PARSE_WAVE, RT_PARSE_HIST = 1, 2
+
+
+def last_route() -> dict:
+    """bnflac_debug_last_route as a dict: the process's last decode launch (route bits RT_*, the
+    four history words it read, the launch count) and its last parse launch (k_parse_wave, whether
+    the history was consulted, the hand-off mode cm, the launch count, the three words read)."""
+    w = (ctypes.c_uint32 * 12)()
+    load().bnflac_debug_last_route(w)
+    r = int(w[0])
+    return {"decode": r, "sys": bool(r & RT_SYS), "fork_before": bool(r & RT_FORK_BEFORE),
+            "fork_after": bool(r & RT_FORK_AFTER), "serial": bool(r & RT_SERIAL), "seg_only": bool(r & RT_SEG_ONLY),
+            "w8split": bool(r & RT_W8SPLIT), "sw": bool(r & RT_SW), "hist_read": bool(r & RT_HIST),
+            "hist": tuple(int(x) for x in w[1:5]), "ndecode": int(w[5]),
+            "parse_wave": bool(w[6] & RT_PARSE_WAVE), "parse_hist_read": bool(w[6] & RT_PARSE_HIST), "cm": int(w[7]),
+            "nparse": int(w[8]), "parse_hist": tuple(int(x) for x in w[9:12])}
 
 
 def md5_interleaved32(pcm: np.ndarray, channels: int, bps: int) -> bytes:

@@ -433,7 +433,10 @@ BNFLAC_API int bnflac_decode_parsed(bnflac_ctx *ctx, const uint8_t *d_bytes, uin
  * The one list of the bits, with what each does and which kernels read it, is
  * birdnest/audio_amd/csrc/bnflac_launch.h (BNF_ABLATE_*).  Each kernel family receives only
  * the bits it defines; the launchers' own mode bits cannot be set from here.  Also read once
- * from BNFLAC_ABLATE in the environment. */
+ * from BNFLAC_ABLATE in the environment.
+ * 0x400 (k_decode_st not launched, k_decode<8> takes every stereo frame) also turns off the
+ * split of k_decode<8> into two launches, as 0x100000 does: with no stereo fast-path frames
+ * the split's two launches would leave most of them undecoded. */
 BNFLAC_API void bnflac_debug_set_ablate(uint32_t flags);
 /* Debug: 1 when the library was built with -DBNFLAC_CRC_FOLD_CHECK (never the shipped one):
  * k_decode_st's tail then computes the frame's CRC-16 both from the running remainder and from
@@ -460,6 +463,25 @@ BNFLAC_API int bnflac_debug_crc_handoff(bnflac_ctx *ctx, uint32_t *out, uint32_t
  * segment grid (k_decode_seg: the previous decode order on the device had neither class)
  * instead of the two full-size side grids. */
 BNFLAC_API uint64_t bnflac_debug_decode_seg_launches(void);
+/* Debug: the route of the process's last decode launch and last parse launch (bnflac_decode_parsed /
+ * bnflac_parse_frames, or the two halves of bnflac_decode_frames), whatever the context or device.
+ * A decode picks its kernels and streams from the class counts the previous decode on the device
+ * left in host memory ("history"), so a test that primes a history reads here that it got the
+ * route it meant.  out12 receives 12 words:
+ *   [0]     the decode: 1 k_decode_sys (+ k_decode_list); otherwise exactly one of 2 side grids forked
+ *           before k_decode_st, 4 forked after it, 8 serial (the W16 / W32 grids on the caller's
+ *           stream), 16 k_decode_seg instead of them; plus 32 k_decode<8> as two launches, 64
+ *           k_decode_sw ran first, 128 the history words were read
+ *   [1..4]  the history words it read (with bit 128): W16 frames, W32 frames, all frames, class-1
+ *           frames of the previous decode order; 0xFFFFFFFF each before the first decode on the device
+ *   [5]     decode launches so far
+ *   [6]     the parse: 1 k_parse_wave ran (it produces no hand-off), 2 the history was consulted
+ *           for the hand-off mode
+ *   [7]     the CRC-16 hand-off mode launched: 0 none, 1 the prefix, 2 and the verdict
+ *   [8]     parse launches so far
+ *   [9..11] the history words the parse read (with bit 2 of [6]): W16, W32, all frames
+ * Written with relaxed host atomics by the launchers: meaningful while one thread launches. */
+BNFLAC_API void bnflac_debug_last_route(uint32_t *out12);
 /* Debug: k_parse_wave's counters, collected while BNFLAC_PW_STATS is set in the environment
  * (passes, splice rounds, serial fallbacks, partitions, frames, scan / window-wait / splice
  * wave-cycles).  out8 holds 8 values; reset != 0 clears them.  0 or -1. */

@@ -107,18 +107,43 @@ from tests.test_gpu_decode_classes import _mixed_batch, _decode
 data, offs, osmp, pcm, total = _mixed_batch(20)
 out, info = _decode(data, offs, osmp, total)
 sys.stdout.buffer.write(out.tobytes())
+# the batch with class-1 frames twice: the second decode has the W = 8 split armed by the first
+from birdnest.audio_amd import libflac
+data, offs, osmp, pcm, total = _mixed_batch(13, class1=True)
+_decode(data, offs, osmp, total)
+out, info = _decode(data, offs, osmp, total)
+sys.stdout.buffer.write(out.tobytes())
+sys.stdout.buffer.write(np.array([libflac.last_route()["decode"]], dtype="<u4").tobytes())
 """
 
 
 @pytest.mark.skipif(not gpu_available(), reason="no GPU")
 @pytest.mark.parametrize("env", [{"BNFLAC_DECODE_SERIAL": "1"}, {"BNFLAC_DECODE_FORK": "1"}])
 def test_side_stream_matches_other_orders(env):
+    """The serial order and the fork after k_decode_st (in a child process: the order is read
+    once) give the bytes of the default order, also for a batch with class-1 frames decoded with
+    the W = 8 split armed; the child reports the order it took (bnflac_debug_last_route)."""
+    from birdnest.audio_amd import libflac
     data, offs, osmp, pcm, total = _mixed_batch(20)
     out, _ = _decode(data, offs, osmp, total)
+    data, offs, osmp, pcm2, total = _mixed_batch(13, class1=True)
+    _decode(data, offs, osmp, total)
+    out2, _ = _decode(data, offs, osmp, total)
+    default = libflac.last_route()
+    assert default["fork_before"] and default["w8split"], default
+    assert np.array_equal(out2.view("<i4").reshape(-1, 2), pcm2)
     r = subprocess.run([sys.executable, "-c", _CHILD, ROOT], env=dict(os.environ, BNFLAC_DECODE_SYS="0", **env),
                        capture_output=True, timeout=100)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
-    assert r.stdout == out.tobytes()
+    n, n2 = len(out.tobytes()), len(out2.tobytes())
+    assert len(r.stdout) == n + n2 + 4
+    assert r.stdout[:n] == out.tobytes()
+    assert r.stdout[n:n + n2] == out2.tobytes()
+    route = int(np.frombuffer(r.stdout[n + n2:], dtype="<u4")[0])
+    if "BNFLAC_DECODE_FORK" in env:
+        assert route & libflac.RT_FORK_AFTER and route & libflac.RT_W8SPLIT, hex(route)
+    else:  # no side streams: no history, no split
+        assert route & libflac.RT_SERIAL and not route & (libflac.RT_W8SPLIT | libflac.RT_HIST), hex(route)
 
 
 def _plain_c2(nframes):

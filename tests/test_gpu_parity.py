@@ -789,18 +789,31 @@ def test_long_rice_prefixes_small_parameters(gpu, fmt_name, decode_mode):
 @LANE
 def test_stereo_handback_matches(gpu, cfg, decode_mode):
     """With k_decode_st disabled (ablation 0x400) every stereo frame goes to k_decode<8>;
-    both routes give identical PCM and frame records."""
+    both routes give identical PCM and frame records.  Each decode follows one of a batch with
+    class-1 frames, which arms the split of k_decode<8> into two launches: 0x400 must turn it
+    off (its two launches would skip the stereo frames outside the block that straddles classes
+    0 and 1; C4's 700 frames put more than three blocks of them there)."""
     from birdnest.audio_amd import synth
+    from tests.test_gpu_decode_classes import _decode as _decode_mixed, _mixed_batch
     torch, libflac, dec = gpu
-    p = synth.config(cfg, nframes={"C4": 64}.get(cfg, 16), last_blocksize=0)
+    p = synth.config(cfg, nframes={"C4": 700}.get(cfg, 16), last_blocksize=0)
     s = synth.encode(p)
     data = s.data.tobytes()
+    primer = _mixed_batch(13, class1=True)
+    _decode_mixed(primer[0], primer[1], primer[2], primer[4])
     out_a, info_a, _ = _decode_batch(gpu, data, s.frame_offsets, libflac.OUT_FLACDECODER)
+    route_a = libflac.last_route()
+    _decode_mixed(primer[0], primer[1], primer[2], primer[4])
     dec.L.bnflac_debug_set_ablate(0x400)
     try:
         out_b, info_b, _ = _decode_batch(gpu, data, s.frame_offsets, libflac.OUT_FLACDECODER)
     finally:
         dec.L.bnflac_debug_set_ablate(0)
+    route_b = libflac.last_route()
+    assert route_a["w8split"] and route_a["hist"][3] != 0, route_a
+    assert not route_b["w8split"] and route_b["hist"] == route_a["hist"], route_b
+    if cfg == "C4":
+        assert ((info_a["flags"] & FL_ST) != 0).sum() > 3 * 32, "class 0 should span whole blocks"
     assert out_a.tobytes() == out_b.tobytes()
     keep = [n for n in info_a.dtype.names if n != "flags"]
     assert all(np.array_equal(info_a[n], info_b[n]) for n in keep)
