@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "bnf_health.h"
+#include "bnf_resample.h"
 #include "bnf_resync.h"
 #include "bnf_select.h"
 #include "bnflac_device.h"
@@ -328,6 +329,17 @@ hipError_t bnf_launch_gather_ranges(const uint8_t *pcm, uint64_t pcm_bytes, uint
 hipError_t bnf_launch_gather_f32(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, uint32_t unit, uint32_t bps,
                                  uint32_t channels, uint32_t flags, const bnf_window *windows, uint32_t nstreams,
                                  uint32_t row_samples, uint64_t plane_pitch, float *out, uint32_t *status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_resample.hip (no tables, no g_stats, no ablate word)
+ * k_gather_f32_rs: the rule of bnf_resample.h.  The planes of k_gather_f32, row_out floats each, hold
+ * the windows filtered to another rate: spec (read here, on the host; refused with
+ * hipErrorInvalidValue when bnf_rsmp_spec_refusal names a cause) and its table taps of spec->up *
+ * spec->taps floats on the device, 16-byte aligned like pcm and out.  Zeroes status (4 words) on s,
+ * then launches with the dynamic LDS the table needs. */
+hipError_t bnf_launch_gather_f32_rs(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, uint32_t unit, uint32_t bps,
+                                    uint32_t channels, uint32_t flags, const bnf_window *windows, uint32_t nstreams,
+                                    const bnf_rsmp_spec *spec, const float *taps, uint32_t row_out, uint64_t plane_pitch,
+                                    float *out, uint32_t *status, hipStream_t s);
 
 /* ------------------------------------------------------------- bnflac_health.hip (no tables, no g_stats, no ablate word)
  * k_hl_*: the rule of bnf_health.h over the records of a decoded selection (sel_info 16-byte aligned),

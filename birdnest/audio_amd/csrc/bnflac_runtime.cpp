@@ -934,6 +934,91 @@ extern "C" BNFLAC_API int bnflac_gather_ranges_f32_host(const uint8_t *pcm, uint
     return 0;
 }
 
+static_assert(sizeof(bnflac_resample_spec) == sizeof(bnf_rsmp_spec) && sizeof(bnf_rsmp_spec) == 16, "bnflac_resample_spec");
+
+extern "C" BNFLAC_API int bnflac_gather_ranges_f32_rs(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
+                                                      const bnflac_stream_params *sp, const bnflac_window *d_windows,
+                                                      uint32_t nstreams, const bnflac_resample_spec *spec,
+                                                      const float *d_taps, uint32_t row_out, uint64_t plane_pitch,
+                                                      uint32_t flags, float *d_out, uint32_t *d_status, void *hs) {
+    if (!ctx || !sp || !spec) return fail("bnflac_gather_ranges_f32_rs: null argument");
+    DevGuard dg(ctx->device); /* the launch on the context's device */
+    if (!d_status || (nstreams && (!d_windows || (row_out && !d_out)))) return fail("bnflac_gather_ranges_f32_rs: null output");
+    if (pcm_bytes && !d_pcm) return fail("bnflac_gather_ranges_f32_rs: null d_pcm");
+    if (!d_taps) return fail("bnflac_gather_ranges_f32_rs: null d_taps");
+    bnf_rsmp_spec rs;
+    memcpy(&rs, spec, sizeof rs);
+    if (const char *why = bnf_rsmp_spec_refusal(rs, row_out)) return fail(std::string("bnflac_gather_ranges_f32_rs: ") + why);
+    uint32_t stride = 0, unit = 0;
+    if (const char *why = gather_f32_refusal(fmt, sp, nstreams, row_out, plane_pitch, flags, stride, unit))
+        return fail(std::string("bnflac_gather_ranges_f32_rs: ") + why);
+    if ((((uintptr_t)d_pcm) | ((uintptr_t)d_out) | ((uintptr_t)d_taps)) & 15u)
+        return fail("bnflac_gather_ranges_f32_rs: d_pcm, d_out and d_taps must be 16-byte aligned");
+    if (((uintptr_t)d_windows) & 7u) return fail("bnflac_gather_ranges_f32_rs: d_windows must be 8-byte aligned");
+    hipError_t e = bnf_launch_gather_f32_rs(d_pcm, pcm_bytes, stride, unit, sp->bps, sp->channels, flags,
+                                            (const bnf_window *)d_windows, nstreams, &rs, d_taps, row_out, plane_pitch, d_out,
+                                            d_status, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_gather_ranges_f32_rs: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_gather_ranges_f32_rs_host(const uint8_t *pcm, uint64_t pcm_bytes, int fmt,
+                                                           const bnflac_stream_params *sp, const bnflac_window *windows,
+                                                           uint32_t nstreams, const bnflac_resample_spec *spec,
+                                                           const float *taps, uint32_t row_out, uint64_t plane_pitch,
+                                                           uint32_t flags, float *out, uint32_t status[4]) {
+    if (!sp || !spec) return fail("bnflac_gather_ranges_f32_rs_host: null argument");
+    if (!status || (nstreams && (!windows || (row_out && !out)))) return fail("bnflac_gather_ranges_f32_rs_host: null output");
+    if (pcm_bytes && !pcm) return fail("bnflac_gather_ranges_f32_rs_host: null pcm");
+    if (!taps) return fail("bnflac_gather_ranges_f32_rs_host: null taps");
+    bnf_rsmp_spec rs;
+    memcpy(&rs, spec, sizeof rs);
+    if (const char *why = bnf_rsmp_spec_refusal(rs, row_out)) return fail(std::string("bnflac_gather_ranges_f32_rs_host: ") + why);
+    uint32_t stride = 0, unit = 0;
+    if (const char *why = gather_f32_refusal(fmt, sp, nstreams, row_out, plane_pitch, flags, stride, unit))
+        return fail(std::string("bnflac_gather_ranges_f32_rs_host: ") + why);
+    if (bnf_gather_f32_rs_host(pcm, pcm_bytes, stride, unit, sp->bps, sp->channels, flags, (const bnf_window *)windows, nstreams,
+                               rs, taps, row_out, plane_pitch, out, status) != 0)
+        return fail("bnflac_gather_ranges_f32_rs_host: out of memory");
+    return 0;
+}
+
+extern "C" BNFLAC_API int64_t bnflac_resample_design(uint32_t rate_in, uint32_t rate_out, double zeros, double rolloff,
+                                                     double beta, bnflac_resample_spec *spec, float *taps, uint64_t taps_cap) {
+    if (!spec) return fail("bnflac_resample_design: null spec");
+    if (!(zeros > 0.0)) zeros = 16.0;
+    if (!(rolloff > 0.0)) rolloff = 0.945;
+    if (!(beta > 0.0)) beta = 9.0;
+    bnf_rsmp_spec rs;
+    uint64_t K = 0;
+    const char *why = bnf_rsmp_design_spec(rate_in, rate_out, zeros, rs, K);
+    if (why) {
+        std::string m = std::string("bnflac_resample_design: ") + why;
+        if (K) m += ": needs up = " + std::to_string(rs.up) + " x taps = " + std::to_string(K) + " (up * taps <= 16384, taps <= 512)";
+        return fail(m);
+    }
+    const int64_t need = (int64_t)rs.up * rs.taps;
+    memcpy(spec, &rs, sizeof rs);
+    if (taps_cap >= (uint64_t)need) {
+        if (!taps) return fail("bnflac_resample_design: null taps");
+        bnf_rsmp_design_taps(rs, rolloff, beta, taps);
+    }
+    return need;
+}
+
+extern "C" BNFLAC_API int bnflac_resample_request(const bnflac_resample_spec *spec, uint64_t j0, uint64_t n_out,
+                                                  uint64_t *first_sample, uint64_t *nsamples, uint32_t *out_first) {
+    if (!spec || !first_sample || !nsamples || !out_first) return fail("bnflac_resample_request: null argument");
+    bnf_rsmp_spec rs;
+    memcpy(&rs, spec, sizeof rs);
+    rs.out_first = 0; /* the spec's own is not read */
+    if (const char *why = bnf_rsmp_spec_refusal(rs, 0)) return fail(std::string("bnflac_resample_request: ") + why);
+    if ((j0 >> 47) || (n_out >> 47) || ((j0 + n_out) >> 47)) return fail("bnflac_resample_request: j0 + n_out must be below 2^47");
+    uint64_t of = 0;
+    bnf_rsmp_request(rs, j0, n_out, *first_sample, *nsamples, of);
+    *out_first = (uint32_t)of; /* below (K / 2 + M + 1) L / M + L < 2^26 */
+    return 0;
+}
+
 /* ====================================================================== */
 /*                 libFLAC-compatible stream decoder                       */
 /* ====================================================================== */

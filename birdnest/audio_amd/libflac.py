@@ -135,6 +135,8 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_window_health", "bnflac_window_health_host",
                  "bnflac_index_streams_resync", "bnflac_resync_plan_host", "bnflac_debug_index_candidates",
                  "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
+                 "bnflac_gather_ranges_f32_rs", "bnflac_gather_ranges_f32_rs_host",
+                 "bnflac_resample_design", "bnflac_resample_request",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -266,6 +268,17 @@ def load() -> ctypes.CDLL:
     L.bnflac_gather_ranges_f32_host.restype = i
     L.bnflac_gather_ranges_f32_host.argtypes = [p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint64, ctypes.c_uint32, p, p]
+    L.bnflac_gather_ranges_f32_rs.restype = i
+    L.bnflac_gather_ranges_f32_rs.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32,
+                                              ctypes.c_uint64, ctypes.c_uint32, p, p, p]
+    L.bnflac_gather_ranges_f32_rs_host.restype = i
+    L.bnflac_gather_ranges_f32_rs_host.argtypes = [p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, p, p, ctypes.c_uint32,
+                                                   ctypes.c_uint64, ctypes.c_uint32, p, p]
+    L.bnflac_resample_design.restype = ctypes.c_int64
+    L.bnflac_resample_design.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_double, p, p, ctypes.c_uint64]
+    L.bnflac_resample_request.restype = i
+    L.bnflac_resample_request.argtypes = [p, ctypes.c_uint64, ctypes.c_uint64, p, p, p]
     _LIB = L
     return L
 
@@ -760,6 +773,76 @@ def gather_ranges_f32_host(pcm: np.ndarray, fmt: int, sp: StreamParams, windows:
     if rc != 0:
         raise RuntimeError(load().bnflac_last_error().decode())
     return out[: n * planes * pitch].reshape(n, planes, pitch)[:, :, :row_samples], status
+
+
+class ResampleSpec(ctypes.Structure):
+    """bnflac_resample_spec: rate_out / rate_in = up / down (coprime), taps per phase, and the output
+    index of a window that lands in row position 0."""
+    _fields_ = [("up", ctypes.c_uint32), ("down", ctypes.c_uint32), ("taps", ctypes.c_uint32),
+                ("out_first", ctypes.c_uint32)]
+
+    def with_out_first(self, out_first: int) -> "ResampleSpec":
+        return ResampleSpec(self.up, self.down, self.taps, out_first)
+
+
+RS_TILE = 1024  # row positions of one output tile of gather_ranges_f32_rs (csrc/bnf_resample.h)
+
+
+def resample_design(rate_in: int, rate_out: int, zeros: float = 0.0, rolloff: float = 0.0, beta: float = 0.0):
+    """A Kaiser-windowed sinc table for gather_ranges_f32_rs (bnflac_resample_design, no GPU); 0 for
+    zeros, rolloff or beta means the default (16, 0.945, 9.0).
+    -> (ResampleSpec with out_first 0, float32[up, taps]); RuntimeError for a zero rate or a table over
+    the limits, with the up and taps the design needs in the message."""
+    L = load()
+    spec = ResampleSpec()
+    need = L.bnflac_resample_design(rate_in, rate_out, zeros, rolloff, beta, ctypes.byref(spec), None, 0)
+    if need < 0:
+        raise RuntimeError(L.bnflac_last_error().decode())
+    taps = np.zeros(need, np.float32)
+    if L.bnflac_resample_design(rate_in, rate_out, zeros, rolloff, beta, ctypes.byref(spec),
+                                taps.ctypes.data_as(ctypes.c_void_p), need) != need:
+        raise RuntimeError(L.bnflac_last_error().decode())
+    return spec, taps.reshape(spec.up, spec.taps)
+
+
+def resample_request(spec: ResampleSpec, j0: int, n_out: int):
+    """The source window of outputs [j0, j0 + n_out) of a stream on the output-rate grid, with the
+    filter's whole support on both sides (bnflac_resample_request).
+    -> (first_sample, nsamples, out_first)"""
+    first, n, of = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+    if load().bnflac_resample_request(ctypes.byref(spec), j0, n_out, ctypes.byref(first), ctypes.byref(n),
+                                      ctypes.byref(of)) != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return first.value, n.value, of.value
+
+
+def gather_ranges_f32_rs_host(pcm: np.ndarray, fmt: int, sp: StreamParams, windows: np.ndarray, spec: ResampleSpec,
+                              taps: np.ndarray, row_out: int, mono: bool = False, plane_pitch: Optional[int] = None,
+                              pcm_bytes: Optional[int] = None):
+    """gather_ranges_f32_rs over host memory (bnflac_gather_ranges_f32_rs_host, no GPU).  pcm, windows:
+    as for gather_ranges_f32_host; taps: float32, spec.up * spec.taps values, phase-major.
+    -> (float32[nstreams, planes, row_out], status uint32[4])"""
+    pcm = np.ascontiguousarray(pcm).view(np.uint8).reshape(-1)
+    nbytes = pcm.size if pcm_bytes is None else min(pcm_bytes, pcm.size)
+    buf = np.zeros((nbytes + 15) // 16 * 16, np.uint8)
+    buf[:nbytes] = pcm[:nbytes]
+    win = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+    tab = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if tab.size != spec.up * spec.taps:
+        raise ValueError("taps holds spec.up * spec.taps values")
+    n = len(win)
+    planes = 1 if mono else sp.channels
+    pitch = row_out if plane_pitch is None else plane_pitch
+    if pitch < row_out:
+        raise ValueError("plane_pitch is below row_out")
+    out = np.zeros(max(n * planes * pitch, 1), np.float32)
+    status = np.zeros(4, np.uint32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    rc = load().bnflac_gather_ranges_f32_rs_host(vp(buf), nbytes, fmt, ctypes.byref(sp), vp(win), n, ctypes.byref(spec),
+                                                 vp(tab), row_out, pitch, F32_MONO if mono else 0, vp(out), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return out[: n * planes * pitch].reshape(n, planes, pitch)[:, :, :row_out], status
 
 
 def streaminfo_md5(data) -> bytes:
@@ -1477,6 +1560,105 @@ class BatchDecoder:
         planes, status["gather"] = self.gather_ranges_f32(d_pcm, fmt, sp, d_win, k, nsamples, mono=mono, stream=s,
                                                           pcm_bytes=pcm_bytes)
         return planes, status
+
+    def gather_ranges_f32_rs(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, spec: ResampleSpec, d_taps,
+                             row_out: int, mono: bool = False, d_out=None, plane_pitch: Optional[int] = None, stream=None,
+                             pcm_bytes=None):
+        """gather_ranges_f32 with the windows filtered to another sample rate in the same launch
+        (bnflac_gather_ranges_f32_rs): row position r of plane c of stream s is output r + spec.out_first
+        of window s's channel c (mono: of the mean of the channels) through the polyphase FIR d_taps,
+        a float32 device tensor of spec.up * spec.taps values, phase-major (resample_design makes one);
+        then zeros.  The other arguments are gather_ranges_f32's, with row_out in row_samples' place.
+        -> (float32[nstreams, planes, row_out], a view of d_out when one is passed; d_status int32[4]),
+        on the device and not synchronised."""
+        import torch
+        dev = d_pcm.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        nbytes = d_pcm.numel() * d_pcm.element_size()
+        planes = 1 if mono else sp.channels
+        pitch = row_out if plane_pitch is None else plane_pitch
+        if pitch < row_out:
+            raise ValueError("plane_pitch is below row_out")
+        if d_taps.dtype != torch.float32 or not d_taps.is_contiguous() or d_taps.numel() != spec.up * spec.taps:
+            raise ValueError("d_taps is a contiguous float32 tensor of spec.up * spec.taps values")
+        with torch.cuda.stream(s):
+            if d_out is None:
+                d_out = torch.zeros(max(nstreams * planes * pitch, 1), dtype=torch.float32, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        if d_out.dtype != torch.float32 or not d_out.is_contiguous():
+            raise ValueError("d_out is a contiguous float32 tensor")
+        if nstreams and d_out.numel() < (nstreams * planes - 1) * pitch + row_out:
+            raise ValueError("d_out is too small for nstreams * planes planes")
+        rc = self.L.bnflac_gather_ranges_f32_rs(self.ctx, ctypes.c_void_p(d_pcm.data_ptr()),
+                                                nbytes if pcm_bytes is None else min(pcm_bytes, nbytes), fmt,
+                                                ctypes.byref(sp), ctypes.c_void_p(d_windows.data_ptr()), nstreams,
+                                                ctypes.byref(spec), ctypes.c_void_p(d_taps.data_ptr()), row_out, pitch,
+                                                F32_MONO if mono else 0, ctypes.c_void_p(d_out.data_ptr()),
+                                                ctypes.c_void_p(d_status.data_ptr()), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        planes_view = torch.as_strided(d_out.view(-1), (nstreams, planes, row_out), (planes * pitch, pitch, 1))
+        return planes_view, d_status
+
+    def decode_crops_f32_rs(self, corpus: Corpus, crops, n_out: int, rate_out: int, fmt: Optional[int] = None,
+                            mono: bool = False, stream=None, shared: bool = True, design=None, zeros: float = 0.0,
+                            rolloff: float = 0.0, beta: float = 0.0):
+        """Crops of an indexed corpus at another sample rate: n_out outputs from output index j0 of a
+        stream's grid at rate_out, as float32 channel planes, with no host synchronisation and nothing
+        read back.  crops: [(stream, j0)], positions at the output rate.  resample_request turns every
+        crop into a source window with the filter's margins, then select_windows[_shared] ->
+        decode_parsed -> gather_ranges_f32_rs; shared (the default) decodes a frame once for all the
+        crops whose margins overlap in it.  A crop past the stream's end is clipped by the selection
+        and gives zeros there, as the whole stream resampled in one window would.
+        design: (ResampleSpec, float32 taps) to use, else resample_design(corpus.sp.sample_rate,
+        rate_out, zeros, rolloff, beta).  One gather launch serves the crops that share an out_first
+        (all of them when every j0 is a multiple of spec.up); the crops are grouped by it.
+        -> (float32[k, planes, n_out] in request order, status: decode_crops' entries, "gather" the sum
+        of the groups' status words with [0] their OR)"""
+        import torch
+        sp = corpus.sp
+        fmt = f32_layout(sp) if fmt is None else fmt
+        if not md5_layout(fmt, sp):
+            raise ValueError("the layout's bytes are not the samples: gather_ranges_f32_rs cannot read it")
+        if n_out < 1:
+            raise ValueError("n_out must be at least 1")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        dev = corpus.d_bytes.device
+        spec, taps = design if design is not None else resample_design(sp.sample_rate, rate_out, zeros, rolloff, beta)
+        k = len(crops)
+        planes = 1 if mono else sp.channels
+        asked = [(int(t), ) + resample_request(spec, int(j0), n_out) for t, j0 in crops]  # (stream, first, n, out_first)
+        order = sorted(range(k), key=lambda i: asked[i][3])
+        requests = [asked[i][:3] for i in order]
+        nsamples = max([r[2] for r in requests] + [1])
+        d_pcm, d_win, _, pcm_bytes, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s, shared)
+        pitch = (n_out + 3) // 4 * 4  # every group's first plane stays 16-byte aligned
+        with torch.cuda.stream(s):
+            d_taps = torch.from_numpy(np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)).to(dev)
+            d_out = torch.zeros(max(k * planes * pitch, 1), dtype=torch.float32, device=dev)
+        sts, g0 = [], 0
+        while g0 < k:
+            g1 = g0
+            while g1 < k and asked[order[g1]][3] == asked[order[g0]][3]:
+                g1 += 1
+            _, st = self.gather_ranges_f32_rs(d_pcm, fmt, sp, d_win[g0 * WINDOW_BYTES:], g1 - g0,
+                                              spec.with_out_first(asked[order[g0]][3]), d_taps, n_out, mono=mono,
+                                              d_out=d_out[g0 * planes * pitch:], plane_pitch=pitch, stream=s,
+                                              pcm_bytes=pcm_bytes)
+            sts.append(st)
+            g0 = g1
+        with torch.cuda.stream(s):
+            out = d_out[: k * planes * pitch].view(k, planes, pitch)[:, :, :n_out]
+            if order != list(range(k)):
+                back = np.empty(k, np.int64)
+                back[np.asarray(order, np.int64)] = np.arange(k)
+                out = out.index_select(0, torch.from_numpy(back).to(dev))
+            if sts:
+                both = torch.stack(sts)
+                status["gather"] = torch.cat([both[:, :1].max(dim=0).values, both[:, 1:].sum(dim=0)]).to(torch.int32)
+            else:
+                status["gather"] = torch.zeros(4, dtype=torch.int32, device=dev)
+        return out, status
 
     def crc_handoff(self, nframes: int) -> np.ndarray:
         """Debug: the CRC-16 hand-off of the last parse_frames call, [nframes, 8] uint32."""

@@ -855,6 +855,82 @@ BNFLAC_API int bnflac_gather_ranges_f32_host(const uint8_t *pcm, uint64_t pcm_by
                                              uint32_t row_samples, uint64_t plane_pitch, uint32_t flags, float *out,
                                              uint32_t status[4]);
 
+/* A rational rate change for bnflac_gather_ranges_f32_rs: rate_out / rate_in = up / down. */
+typedef struct {
+    uint32_t up, down;  /* L, M: rate_out / g, rate_in / g, g = gcd(rate_in, rate_out); coprime, 1..65535 */
+    uint32_t taps;      /* K: taps per phase, a multiple of 4 in 4..512, up * taps <= 16384 */
+    uint32_t out_first; /* output index of the window that lands in row position 0, below 2^31 */
+} bnflac_resample_spec; /* 16 bytes */
+
+/* bnflac_gather_ranges_f32 with the windows filtered to another sample rate in the same launch: a
+ * polyphase FIR whose table the caller passes.  d_taps is a device table of spec->up * spec->taps
+ * float32, phase-major: h[phase][k] at phase * taps + k.  The contract is in terms of the table's
+ * float32 values, whoever made them (bnflac_resample_design makes a Kaiser-windowed sinc).
+ * Layouts, the window check, the plane layout, MONO and the status words are those of
+ * bnflac_gather_ranges_f32, with row_out in row_samples' place.  Per window s that passes the check,
+ * with n its nsamples, L = up, M = down, K = taps: x[i] for 0 <= i < n is the float
+ * bnflac_gather_ranges_f32 specifies for sample frame i of the plane ((float)v * 2^-(bps-1) for channel
+ * c, or the mono rule with BNFLAC_F32_MONO), and x[i] = +0.0f for every other i.  A window is filtered
+ * on its own: nothing outside it is read.
+ *   n_out = max(0, ceil(n L / M) - out_first), ncopy = min(n_out, row_out).
+ *   Row position r < ncopy is output j = r + out_first: q = floor(j M / L), phase = (j M) mod L,
+ *   c0 = K / 2 - 1.  Four float32 accumulators start at +0.0f; for k = 0 .. K - 1 ascending
+ *       a[k & 3] = fmaf(h[phase][k], x[q + k - c0], a[k & 3])        (one rounding per term)
+ *   and the value is (a[0] + a[1]) + (a[2] + a[3]), each + one float32 addition.
+ *   Row positions [ncopy, row_out) are +0.0f; floats from row_out to plane_pitch are not written.
+ * Values are these bit for bit, on the device and in bnflac_gather_ranges_f32_rs_host.
+ * d_status (device, 4 words): [0] bit 0 some bad window, [1] how many, [2] windows with n_out >
+ * row_out, [3] 0.  nstreams == 0 writes a zero status.
+ * Refused (a negative return, the cause in bnflac_last_error(), nothing launched, nothing written):
+ * everything bnflac_gather_ranges_f32 refuses (layouts, channels outside 1..8, flag bits other than
+ * BNFLAC_F32_MONO, plane_pitch < row_out, alignments, nstreams >= 2^30, null arguments); a null spec or
+ * d_taps; up or down outside 1..65535 or not coprime; taps outside 4..512 or no multiple of 4;
+ * up * taps > 16384; row_out or out_first not below 2^31; d_taps not 16-byte aligned.
+ * spec is read on the host at call time.  No trip count or address depends on a window's contents
+ * beyond the check.  Asynchronous on hip_stream, no host synchronisation, no allocation; the launch
+ * runs on ctx's device.  The output tile is 1,024 row positions of one window. */
+BNFLAC_API int bnflac_gather_ranges_f32_rs(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int out_format,
+                                           const bnflac_stream_params *sp, const bnflac_window *d_windows, uint32_t nstreams,
+                                           const bnflac_resample_spec *spec, const float *d_taps, uint32_t row_out,
+                                           uint64_t plane_pitch, uint32_t flags, float *d_out, uint32_t *d_status,
+                                           void *hip_stream);
+
+/* The same planes and status from host memory, by the same code (csrc/bnf_resample.h); no GPU needed.
+ * Refuses what the device call refuses apart from pointer alignment (out and taps need a float's).
+ * 0 or -1. */
+BNFLAC_API int bnflac_gather_ranges_f32_rs_host(const uint8_t *pcm, uint64_t pcm_bytes, int out_format,
+                                                const bnflac_stream_params *sp, const bnflac_window *windows,
+                                                uint32_t nstreams, const bnflac_resample_spec *spec, const float *taps,
+                                                uint32_t row_out, uint64_t plane_pitch, uint32_t flags, float *out,
+                                                uint32_t status[4]);
+
+/* A table for bnflac_gather_ranges_f32_rs: a Kaiser-windowed sinc.  Host only, no GPU.  Fills spec
+ * (out_first = 0), returns the floats the table needs, up * taps, and writes them to taps when
+ * taps_cap is at least that (so a call with taps_cap = 0 sizes the table).  zeros: zero crossings of
+ * the sinc on each side (default 16); rolloff: the cutoff as a fraction of the lower Nyquist
+ * frequency (default 0.945); beta: the Kaiser window's (default 9.0); a value <= 0 means the default.
+ * In double, with L = up, M = down:  s = min(1, L / M), fc = rolloff * s,
+ * K = round_up(2 * ceil(zeros / s), 4), c0 = K / 2 - 1, tau = (k - c0) - phase / L,
+ * w = I0(beta * sqrt(1 - (tau / (K/2))^2)) / I0(beta) for |tau| < K / 2, else 0,
+ * g = fc * sinc(fc * tau) * w with sinc(x) = sin(pi x) / (pi x), h[phase][k] = (float)(g / sum_k g):
+ * every phase has unit gain at DC.  Equal rates give {1, 1, 4} and the table {0, 1, 0, 0}, the identity.
+ * A negative return for a zero rate, a null spec, or a table over the gather's limits; then
+ * bnflac_last_error() states the up and taps the design needs, so a caller can lower zeros. */
+BNFLAC_API int64_t bnflac_resample_design(uint32_t rate_in, uint32_t rate_out, double zeros, double rolloff, double beta,
+                                          bnflac_resample_spec *spec, float *taps, uint64_t taps_cap);
+
+/* The source window for outputs [j0, j0 + n_out) of a stream on the output-rate grid, with the
+ * filter's whole support on both sides.  Host only.  With c0 = K / 2 - 1:
+ *   b = max(0, floor(j0 M / L) - c0) / M (an integer division), first_sample = M b,
+ *   out_first = j0 - L b, nsamples = floor((j0 + n_out - 1) M / L) + K / 2 + 1 - first_sample
+ *   (0 for n_out = 0).
+ * The window starts on a multiple of M, so its output grid is the stream's: a request of
+ * (stream, first_sample, nsamples) and a spec with this out_first give the same values as the same
+ * outputs of the whole stream, whose end the selection's clipping supplies.  spec's own out_first is
+ * not read.  0, or -1 for a null argument, a spec the gather refuses or j0 + n_out >= 2^47. */
+BNFLAC_API int bnflac_resample_request(const bnflac_resample_spec *spec, uint64_t j0, uint64_t n_out, uint64_t *first_sample,
+                                       uint64_t *nsamples, uint32_t *out_first);
+
 /* ======================== Part 3: streaming reader ======================= */
 
 /* The fast path under FLACDecoder.Read (FLACDecoder.cs:124-205) and OpenAL's buffer fill
