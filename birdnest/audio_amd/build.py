@@ -37,6 +37,7 @@ HIP_TUS = [
     ("bnflac_select.hip", [], "bnflac_select"),  # k_sel_*, k_win_*, k_shr_*, k_gather_ranges (no CRC tables, no g_stats)
     ("bnflac_f32.hip", [], "bnflac_f32"),  # k_gather_f32 (no CRC tables, no g_stats)
     ("bnflac_resample.hip", [], "bnflac_resample"),  # k_gather_f32_rs (no CRC tables, no g_stats)
+    ("bnflac_mel.hip", [], "bnflac_mel"),  # k_gather_mel (no CRC tables, no g_stats)
     ("bnflac_health.hip", [], "bnflac_health"),  # k_hl_* (no CRC tables, no g_stats)
     ("bnflac_resync.hip", [], "bnflac_resync"),  # k_rs_* (no CRC tables, no g_stats)
     ("bnflac_runtime.cpp", [], "bnflac_runtime"),

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "bnf_health.h"
+#include "bnf_mel.h"
 #include "bnf_resample.h"
 #include "bnf_resync.h"
 #include "bnf_select.h"
@@ -340,6 +341,17 @@ hipError_t bnf_launch_gather_f32_rs(const uint8_t *pcm, uint64_t pcm_bytes, uint
                                     uint32_t channels, uint32_t flags, const bnf_window *windows, uint32_t nstreams,
                                     const bnf_rsmp_spec *spec, const float *taps, uint32_t row_out, uint64_t plane_pitch,
                                     float *out, uint32_t *status, hipStream_t s);
+
+/* ------------------------------------------------------------- bnflac_mel.hip (no tables, no g_stats, no ablate word)
+ * k_gather_mel: the rule of bnf_mel.h.  Per window and plane, rows of row_frames floats frame_pitch
+ * apart: the power spectrum or the band sums of the window's STFT frames.  spec is read here, on the
+ * host (hipErrorInvalidValue when bnf_mel_spec_refusal names a cause or bands is missing); tab
+ * (window, twiddles, weights; 16-byte aligned like pcm) and bands are device tables.  Zeroes status
+ * (4 words) on s, then launches with the dynamic LDS bnf_mel_plan_of names. */
+hipError_t bnf_launch_gather_mel(const uint8_t *pcm, uint64_t pcm_bytes, uint32_t stride, uint32_t unit, uint32_t bps,
+                                 uint32_t channels, uint32_t flags, const bnf_window *windows, uint32_t nstreams,
+                                 const bnf_mel_spec *spec, const float *tab, const uint32_t *bands, uint32_t row_frames,
+                                 uint64_t frame_pitch, float *out, uint32_t *status, hipStream_t s);
 
 /* ------------------------------------------------------------- bnflac_health.hip (no tables, no g_stats, no ablate word)
  * k_hl_*: the rule of bnf_health.h over the records of a decoded selection (sel_info 16-byte aligned),

@@ -1019,6 +1019,93 @@ extern "C" BNFLAC_API int bnflac_resample_request(const bnflac_resample_spec *sp
     return 0;
 }
 
+static_assert(sizeof(bnflac_mel_spec) == sizeof(bnf_mel_spec) && sizeof(bnf_mel_spec) == 32, "bnflac_mel_spec");
+
+extern "C" BNFLAC_API int bnflac_gather_ranges_mel(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int fmt,
+                                                   const bnflac_stream_params *sp, const bnflac_window *d_windows,
+                                                   uint32_t nstreams, const bnflac_mel_spec *spec, const float *d_tab,
+                                                   const uint32_t *d_bands, uint32_t row_frames, uint64_t frame_pitch,
+                                                   uint32_t flags, float *d_out, uint32_t *d_status, void *hs) {
+    if (!ctx || !sp || !spec) return fail("bnflac_gather_ranges_mel: null argument");
+    DevGuard dg(ctx->device); /* the launch on the context's device */
+    if (!d_status || (nstreams && (!d_windows || (row_frames && !d_out)))) return fail("bnflac_gather_ranges_mel: null output");
+    if (pcm_bytes && !d_pcm) return fail("bnflac_gather_ranges_mel: null d_pcm");
+    if (!d_tab) return fail("bnflac_gather_ranges_mel: null d_tab");
+    bnf_mel_spec ms;
+    memcpy(&ms, spec, sizeof ms);
+    if (ms.n_mels && !d_bands) return fail("bnflac_gather_ranges_mel: null d_bands with n_mels != 0");
+    uint32_t stride = 0, unit = 0;
+    if (const char *why = gather_f32_refusal(fmt, sp, nstreams, 0, 0, flags, stride, unit))
+        return fail(std::string("bnflac_gather_ranges_mel: ") + why);
+    if (const char *why = bnf_mel_spec_refusal(ms, row_frames, frame_pitch)) return fail(std::string("bnflac_gather_ranges_mel: ") + why);
+    if ((((uintptr_t)d_pcm) | ((uintptr_t)d_out) | ((uintptr_t)d_tab)) & 15u)
+        return fail("bnflac_gather_ranges_mel: d_pcm, d_out and d_tab must be 16-byte aligned");
+    if (((uintptr_t)d_windows) & 7u) return fail("bnflac_gather_ranges_mel: d_windows must be 8-byte aligned");
+    if (((uintptr_t)d_bands) & 3u) return fail("bnflac_gather_ranges_mel: d_bands must be 4-byte aligned");
+    hipError_t e = bnf_launch_gather_mel(d_pcm, pcm_bytes, stride, unit, sp->bps, sp->channels, flags,
+                                         (const bnf_window *)d_windows, nstreams, &ms, d_tab, d_bands, row_frames, frame_pitch,
+                                         d_out, d_status, (hipStream_t)hs);
+    return e == hipSuccess ? 0 : fail(std::string("bnflac_gather_ranges_mel: ") + hipGetErrorString(e));
+}
+
+extern "C" BNFLAC_API int bnflac_gather_ranges_mel_host(const uint8_t *pcm, uint64_t pcm_bytes, int fmt,
+                                                        const bnflac_stream_params *sp, const bnflac_window *windows,
+                                                        uint32_t nstreams, const bnflac_mel_spec *spec, const float *tab,
+                                                        const uint32_t *bands, uint32_t row_frames, uint64_t frame_pitch,
+                                                        uint32_t flags, float *out, uint32_t status[4]) {
+    if (!sp || !spec) return fail("bnflac_gather_ranges_mel_host: null argument");
+    if (!status || (nstreams && (!windows || (row_frames && !out)))) return fail("bnflac_gather_ranges_mel_host: null output");
+    if (pcm_bytes && !pcm) return fail("bnflac_gather_ranges_mel_host: null pcm");
+    if (!tab) return fail("bnflac_gather_ranges_mel_host: null tab");
+    bnf_mel_spec ms;
+    memcpy(&ms, spec, sizeof ms);
+    if (ms.n_mels && !bands) return fail("bnflac_gather_ranges_mel_host: null bands with n_mels != 0");
+    uint32_t stride = 0, unit = 0;
+    if (const char *why = gather_f32_refusal(fmt, sp, nstreams, 0, 0, flags, stride, unit))
+        return fail(std::string("bnflac_gather_ranges_mel_host: ") + why);
+    if (const char *why = bnf_mel_spec_refusal(ms, row_frames, frame_pitch))
+        return fail(std::string("bnflac_gather_ranges_mel_host: ") + why);
+    if (bnf_gather_mel_host(pcm, pcm_bytes, stride, unit, sp->bps, sp->channels, flags, (const bnf_window *)windows, nstreams, ms,
+                            tab, bands, row_frames, frame_pitch, out, status) != 0)
+        return fail("bnflac_gather_ranges_mel_host: out of memory");
+    return 0;
+}
+
+extern "C" BNFLAC_API int64_t bnflac_mel_design(uint32_t sample_rate, uint32_t n_fft, uint32_t hop, uint32_t n_mels, double f_min,
+                                                double f_max, bnflac_mel_spec *spec, float *tab, uint64_t tab_cap,
+                                                uint32_t *bands, uint64_t bands_cap) {
+    if (!spec) return fail("bnflac_mel_design: null spec");
+    if (!(f_max > 0.0)) f_max = (double)sample_rate / 2.0;
+    bnf_mel_spec ms;
+    uint64_t nw = 0;
+    const char *why = bnf_mel_design_spec(sample_rate, n_fft, hop, n_mels, f_min, f_max, ms, nw);
+    if (why) {
+        std::string m = std::string("bnflac_mel_design: ") + why;
+        if (nw || n_mels > BNF_MEL_MAX_MELS)
+            m += ": needs n_mels = " + std::to_string(n_mels) + " and n_weights = " + std::to_string(nw) +
+                 " (n_mels <= 256, n_weights <= 8192)";
+        return fail(m);
+    }
+    const int64_t need = 2 * (int64_t)ms.n_fft + ms.n_weights;
+    memcpy(spec, &ms, sizeof ms);
+    if (tab_cap >= (uint64_t)need && bands_cap >= (ms.n_mels ? 2u * ((uint64_t)ms.n_mels + 1u) : 0u)) {
+        if (!tab || (ms.n_mels && !bands)) return fail("bnflac_mel_design: null table");
+        bnf_mel_design_tables(sample_rate, ms, f_min, f_max, tab, bands);
+    }
+    return need;
+}
+
+extern "C" BNFLAC_API int bnflac_mel_request(const bnflac_mel_spec *spec, uint64_t t0, uint64_t n_frames, uint64_t *first_sample,
+                                             uint64_t *nsamples, int32_t *origin) {
+    if (!spec || !first_sample || !nsamples || !origin) return fail("bnflac_mel_request: null argument");
+    bnf_mel_spec ms;
+    memcpy(&ms, spec, sizeof ms);
+    if (const char *why = bnf_mel_spec_refusal(ms, 0, 0)) return fail(std::string("bnflac_mel_request: ") + why);
+    if ((t0 >> 31) || (n_frames >> 31) || ((t0 + n_frames) >> 31)) return fail("bnflac_mel_request: t0 + n_frames must be below 2^31");
+    bnf_mel_request(ms, t0, n_frames, *first_sample, *nsamples, *origin);
+    return 0;
+}
+
 /* ====================================================================== */
 /*                 libFLAC-compatible stream decoder                       */
 /* ====================================================================== */

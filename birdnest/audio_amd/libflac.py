@@ -137,6 +137,7 @@ BATCH_SYMBOLS = ["bnflac_ctx_create", "bnflac_ctx_destroy", "bnflac_last_error",
                  "bnflac_gather_ranges_f32", "bnflac_gather_ranges_f32_host",
                  "bnflac_gather_ranges_f32_rs", "bnflac_gather_ranges_f32_rs_host",
                  "bnflac_resample_design", "bnflac_resample_request",
+                 "bnflac_gather_ranges_mel", "bnflac_gather_ranges_mel_host", "bnflac_mel_design", "bnflac_mel_request",
                  "bnflac_debug_set_crc_mode", "bnflac_debug_crc_handoff"]
 READER_SYMBOLS = ["bnflac_reader_open", "bnflac_reader_params", "bnflac_reader_read", "bnflac_reader_close",
                   "bnflac_reader_last_error", "bnflac_reader_seek", "bnflac_reader_read_filereader",
@@ -279,6 +280,17 @@ def load() -> ctypes.CDLL:
                                          ctypes.c_double, p, p, ctypes.c_uint64]
     L.bnflac_resample_request.restype = i
     L.bnflac_resample_request.argtypes = [p, ctypes.c_uint64, ctypes.c_uint64, p, p, p]
+    L.bnflac_gather_ranges_mel.restype = i
+    L.bnflac_gather_ranges_mel.argtypes = [p, p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, p, p, p, ctypes.c_uint32,
+                                           ctypes.c_uint64, ctypes.c_uint32, p, p, p]
+    L.bnflac_gather_ranges_mel_host.restype = i
+    L.bnflac_gather_ranges_mel_host.argtypes = [p, ctypes.c_uint64, i, p, p, ctypes.c_uint32, p, p, p, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.c_uint32, p, p]
+    L.bnflac_mel_design.restype = ctypes.c_int64
+    L.bnflac_mel_design.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double,
+                                    ctypes.c_double, p, p, ctypes.c_uint64, p, ctypes.c_uint64]
+    L.bnflac_mel_request.restype = i
+    L.bnflac_mel_request.argtypes = [p, ctypes.c_uint64, ctypes.c_uint64, p, p, p]
     _LIB = L
     return L
 
@@ -843,6 +855,103 @@ def gather_ranges_f32_rs_host(pcm: np.ndarray, fmt: int, sp: StreamParams, windo
     if rc != 0:
         raise RuntimeError(load().bnflac_last_error().decode())
     return out[: n * planes * pitch].reshape(n, planes, pitch)[:, :, :row_out], status
+
+
+class MelSpec(ctypes.Structure):
+    """bnflac_mel_spec: the FFT size, the hop, the bands (0: the power spectrum's bins), the sample
+    index of tap 0 of frame 0 relative to the window, and the floats of the band weights."""
+    _fields_ = [("n_fft", ctypes.c_uint32), ("hop", ctypes.c_uint32), ("n_mels", ctypes.c_uint32),
+                ("origin", ctypes.c_int32), ("n_weights", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+    @property
+    def rows(self) -> int:
+        return self.n_mels if self.n_mels else self.n_fft // 2 + 1
+
+    def with_origin(self, origin: int) -> "MelSpec":
+        return MelSpec(self.n_fft, self.hop, self.n_mels, origin, self.n_weights)
+
+
+MEL_TILE = 32  # frames of one output tile of gather_ranges_mel (csrc/bnf_mel.h)
+
+
+def mel_design(sample_rate: int, n_fft: int, hop: int, n_mels: int, f_min: float = 0.0, f_max: float = 0.0):
+    """The tables of gather_ranges_mel (bnflac_mel_design, no GPU): a periodic Hann window, the
+    twiddles and HTK mel triangles with their zero weights dropped; f_max 0 means sample_rate / 2,
+    n_mels 0 the power spectrum.
+    -> (MelSpec with origin -(n_fft // 2), tab float32[2 n_fft + n_weights], bands uint32[n_mels + 1, 2]
+    or uint32[0, 2]); RuntimeError for a design over the limits, with what it needs in the message."""
+    L = load()
+    spec = MelSpec()
+    need = L.bnflac_mel_design(sample_rate, n_fft, hop, n_mels, f_min, f_max, ctypes.byref(spec), None, 0, None, 0)
+    if need < 0:
+        raise RuntimeError(L.bnflac_last_error().decode())
+    tab = np.zeros(need, np.float32)
+    bands = np.zeros((n_mels + 1 if n_mels else 0, 2), np.uint32)
+    if L.bnflac_mel_design(sample_rate, n_fft, hop, n_mels, f_min, f_max, ctypes.byref(spec),
+                           tab.ctypes.data_as(ctypes.c_void_p), need,
+                           bands.ctypes.data_as(ctypes.c_void_p) if bands.size else None, bands.size) != need:
+        raise RuntimeError(L.bnflac_last_error().decode())
+    return spec, tab, bands
+
+
+def mel_to_device(mel, device):
+    """(MelSpec, tab, bands) as mel_design returns them -> (MelSpec, float32 device tensor, int32 device
+    tensor or None when n_mels is 0): the tables of gather_ranges_mel, uploaded once.  Tensors that
+    are already on a device pass through."""
+    import torch
+    spec, tab, bands = mel
+    if not isinstance(tab, torch.Tensor):
+        tab = torch.from_numpy(np.ascontiguousarray(tab, dtype=np.float32).reshape(-1)).to(device)
+    if not spec.n_mels:
+        bands = None
+    elif not isinstance(bands, torch.Tensor):
+        bands = torch.from_numpy(np.ascontiguousarray(bands, dtype=np.uint32).reshape(-1).view(np.int32)).to(device)
+    return spec, tab, bands
+
+
+def mel_request(spec: MelSpec, t0: int, n_frames: int):
+    """The source window of frames [t0, t0 + n_frames) of a stream's own frame grid, with the whole
+    support of every frame (bnflac_mel_request).
+    -> (first_sample, nsamples, origin)"""
+    first, n, origin = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int32()
+    if load().bnflac_mel_request(ctypes.byref(spec), t0, n_frames, ctypes.byref(first), ctypes.byref(n),
+                                 ctypes.byref(origin)) != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return first.value, n.value, origin.value
+
+
+def gather_ranges_mel_host(pcm: np.ndarray, fmt: int, sp: StreamParams, windows: np.ndarray, spec: MelSpec, tab: np.ndarray,
+                           bands: Optional[np.ndarray], row_frames: int, mono: bool = False,
+                           frame_pitch: Optional[int] = None, pcm_bytes: Optional[int] = None):
+    """gather_ranges_mel over host memory (bnflac_gather_ranges_mel_host, no GPU).  pcm, windows: as
+    for gather_ranges_f32_host; tab: float32, 2 n_fft + n_weights values; bands: uint32, n_mels + 1
+    pairs (None when n_mels is 0).
+    -> (float32[nstreams, planes, rows, row_frames], status uint32[4])"""
+    pcm = np.ascontiguousarray(pcm).view(np.uint8).reshape(-1)
+    nbytes = pcm.size if pcm_bytes is None else min(pcm_bytes, pcm.size)
+    buf = np.zeros((nbytes + 15) // 16 * 16, np.uint8)
+    buf[:nbytes] = pcm[:nbytes]
+    win = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+    tab = np.ascontiguousarray(tab, dtype=np.float32).reshape(-1)
+    if tab.size != 2 * spec.n_fft + spec.n_weights:
+        raise ValueError("tab holds 2 * n_fft + n_weights values")
+    bnd = np.zeros(0, np.uint32) if bands is None else np.ascontiguousarray(bands, dtype=np.uint32).reshape(-1)
+    if bnd.size != (2 * (spec.n_mels + 1) if spec.n_mels else bnd.size):
+        raise ValueError("bands holds n_mels + 1 pairs")
+    n = len(win)
+    planes = 1 if mono else sp.channels
+    rows = spec.rows
+    pitch = row_frames if frame_pitch is None else frame_pitch
+    if pitch < row_frames:
+        raise ValueError("frame_pitch is below row_frames")
+    out = np.zeros(max(n * planes * rows * pitch, 1), np.float32)
+    status = np.zeros(4, np.uint32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
+    rc = load().bnflac_gather_ranges_mel_host(vp(buf), nbytes, fmt, ctypes.byref(sp), vp(win), n, ctypes.byref(spec), vp(tab),
+                                              vp(bnd), row_frames, pitch, F32_MONO if mono else 0, vp(out), vp(status))
+    if rc != 0:
+        raise RuntimeError(load().bnflac_last_error().decode())
+    return out[: n * planes * rows * pitch].reshape(n, planes, rows, pitch)[:, :, :, :row_frames], status
 
 
 def streaminfo_md5(data) -> bytes:
@@ -1656,6 +1765,124 @@ class BatchDecoder:
             if sts:
                 both = torch.stack(sts)
                 status["gather"] = torch.cat([both[:, :1].max(dim=0).values, both[:, 1:].sum(dim=0)]).to(torch.int32)
+            else:
+                status["gather"] = torch.zeros(4, dtype=torch.int32, device=dev)
+        return out, status
+
+    def gather_ranges_mel(self, d_pcm, fmt: int, sp: StreamParams, d_windows, nstreams: int, spec: MelSpec, d_tab, d_bands,
+                          row_frames: int, mono: bool = False, d_out=None, frame_pitch: Optional[int] = None, stream=None,
+                          pcm_bytes=None):
+        """The windows of a decoded selection as mel (or power) spectrogram planes in one launch
+        (bnflac_gather_ranges_mel): column t of row r of plane c of stream s is band r (bin r when
+        spec.n_mels is 0) of STFT frame t of window s's channel c (mono: of the mean of the channels),
+        frame t starting at sample spec.origin + t * spec.hop of the window; then zeros.  d_tab: a
+        float32 device tensor of 2 * n_fft + n_weights values (window, twiddles, weights); d_bands: an
+        int32 device tensor of n_mels + 1 pairs, or None when n_mels is 0 (mel_design makes both).
+        The other arguments are gather_ranges_f32's, with row_frames and frame_pitch in row_samples'
+        and plane_pitch's place.
+        -> (float32[nstreams, planes, rows, row_frames], a view of d_out when one is passed; d_status
+        int32[4]), on the device and not synchronised."""
+        import torch
+        dev = d_pcm.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        nbytes = d_pcm.numel() * d_pcm.element_size()
+        planes = 1 if mono else sp.channels
+        rows = spec.rows
+        pitch = row_frames if frame_pitch is None else frame_pitch
+        if pitch < row_frames:
+            raise ValueError("frame_pitch is below row_frames")
+        if d_tab.dtype != torch.float32 or not d_tab.is_contiguous() or d_tab.numel() != 2 * spec.n_fft + spec.n_weights:
+            raise ValueError("d_tab is a contiguous float32 tensor of 2 * n_fft + n_weights values")
+        if spec.n_mels and (d_bands is None or d_bands.element_size() != 4 or not d_bands.is_contiguous()
+                            or d_bands.numel() != 2 * (spec.n_mels + 1)):
+            raise ValueError("d_bands is a contiguous 32-bit tensor of n_mels + 1 pairs")
+        with torch.cuda.stream(s):
+            if d_out is None:
+                d_out = torch.zeros(max(nstreams * planes * rows * pitch, 1), dtype=torch.float32, device=dev)
+            d_status = torch.zeros(4, dtype=torch.int32, device=dev)
+        if d_out.dtype != torch.float32 or not d_out.is_contiguous():
+            raise ValueError("d_out is a contiguous float32 tensor")
+        if nstreams and d_out.numel() < (nstreams * planes * rows - 1) * pitch + row_frames:
+            raise ValueError("d_out is too small for nstreams * planes * rows rows")
+        rc = self.L.bnflac_gather_ranges_mel(self.ctx, ctypes.c_void_p(d_pcm.data_ptr()),
+                                             nbytes if pcm_bytes is None else min(pcm_bytes, nbytes), fmt,
+                                             ctypes.byref(sp), ctypes.c_void_p(d_windows.data_ptr()), nstreams,
+                                             ctypes.byref(spec), ctypes.c_void_p(d_tab.data_ptr()),
+                                             ctypes.c_void_p(d_bands.data_ptr()) if spec.n_mels else None, row_frames, pitch,
+                                             F32_MONO if mono else 0, ctypes.c_void_p(d_out.data_ptr()),
+                                             ctypes.c_void_p(d_status.data_ptr()), self._stream(s))
+        if rc != 0:
+            raise RuntimeError(self.L.bnflac_last_error().decode())
+        view = torch.as_strided(d_out.view(-1), (nstreams, planes, rows, row_frames),
+                                (planes * rows * pitch, rows * pitch, pitch, 1))
+        return view, d_status
+
+    def decode_crops_mel(self, corpus: Corpus, crops, n_frames: int, mel, fmt: Optional[int] = None, mono: bool = False,
+                         health: bool = False, stream=None, shared: bool = True):
+        """Crops of an indexed corpus as mel (or power) spectrograms: n_frames STFT frames from frame
+        t0 of a stream's own frame grid, with nothing read back.
+        crops: [(stream, t0)]; mel: (MelSpec, tab, bands) as mel_design returns them, or with tab and
+        bands already on the device (mel_to_device: upload them once and pass them to every call; host
+        tables are uploaded again by each call, a blocking copy).  The requests, and the permutation
+        when the crops have several origins, are uploaded from host memory per call as in decode_crops;
+        apart from those copies nothing waits for the device.  mel_request
+        turns every crop into a source window with the whole support of its frames, then
+        select_windows[_shared] -> decode_parsed -> gather_ranges_mel; shared (the default) decodes a
+        frame once for all the crops that overlap in it.  A crop past the stream's end is clipped by
+        the selection and gives zeros there, as the whole stream in one window would.  One gather
+        launch serves the crops that share an origin (all that do not start in front of the stream's
+        sample 0); the crops are grouped by it.  health: as for decode_crops, over the source windows.
+        -> (float32[k, planes, rows, n_frames] in request order, status: decode_crops' entries,
+        "gather" the sum of the groups' status words with [0] their OR and [3] the bad bands)"""
+        import torch
+        sp = corpus.sp
+        fmt = f32_layout(sp) if fmt is None else fmt
+        if not md5_layout(fmt, sp):
+            raise ValueError("the layout's bytes are not the samples: gather_ranges_mel cannot read it")
+        if n_frames < 1:
+            raise ValueError("n_frames must be at least 1")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        dev = corpus.d_bytes.device
+        spec, tab, bands = mel
+        k = len(crops)
+        planes = 1 if mono else sp.channels
+        rows = spec.rows
+        asked = [(int(t), ) + mel_request(spec, int(t0), n_frames) for t, t0 in crops]  # (stream, first, n, origin)
+        order = sorted(range(k), key=lambda i: asked[i][3])
+        requests = [asked[i][:3] for i in order]
+        nsamples = max([r[2] for r in requests] + [1])
+        d_pcm, d_win, _, pcm_bytes, status = self._decode_crop_selection(corpus, requests, nsamples, fmt, s, shared,
+                                                                         health=health)
+        pitch = (n_frames + 3) // 4 * 4  # every group's first row stays 16-byte aligned
+        with torch.cuda.stream(s):
+            _, d_tab, d_bands = mel_to_device(mel, dev)
+            d_back = None
+            if order != list(range(k)):  # the rows and the records back in request order: one upload
+                back = np.empty(k, np.int64)
+                back[np.asarray(order, np.int64)] = np.arange(k)
+                d_back = torch.from_numpy(back).to(dev)
+                if health:
+                    status["windows_health"] = status["windows_health"].index_select(0, d_back)
+            d_out = torch.zeros(max(k * planes * rows * pitch, 1), dtype=torch.float32, device=dev)
+        sts, g0 = [], 0
+        while g0 < k:
+            g1 = g0
+            while g1 < k and asked[order[g1]][3] == asked[order[g0]][3]:
+                g1 += 1
+            _, st = self.gather_ranges_mel(d_pcm, fmt, sp, d_win[g0 * WINDOW_BYTES:], g1 - g0,
+                                           spec.with_origin(asked[order[g0]][3]), d_tab, d_bands, n_frames, mono=mono,
+                                           d_out=d_out[g0 * planes * rows * pitch:], frame_pitch=pitch, stream=s,
+                                           pcm_bytes=pcm_bytes)
+            sts.append(st)
+            g0 = g1
+        with torch.cuda.stream(s):
+            out = d_out[: k * planes * rows * pitch].view(k, planes, rows, pitch)[:, :, :, :n_frames]
+            if d_back is not None:
+                out = out.index_select(0, d_back)
+            if sts:
+                both = torch.stack(sts)
+                status["gather"] = torch.cat([both[:, :1].max(dim=0).values, both[:, 1:3].sum(dim=0),
+                                              both[:, 3:].max(dim=0).values]).to(torch.int32)
             else:
                 status["gather"] = torch.zeros(4, dtype=torch.int32, device=dev)
         return out, status

@@ -931,6 +931,124 @@ BNFLAC_API int64_t bnflac_resample_design(uint32_t rate_in, uint32_t rate_out, d
 BNFLAC_API int bnflac_resample_request(const bnflac_resample_spec *spec, uint64_t j0, uint64_t n_out, uint64_t *first_sample,
                                        uint64_t *nsamples, uint32_t *out_first);
 
+/* An STFT and band projection for bnflac_gather_ranges_mel. */
+typedef struct {
+    uint32_t n_fft;       /* N: a power of two, 64..2048 */
+    uint32_t hop;         /* 1..65535 */
+    uint32_t n_mels;      /* 0..256; 0: the rows are the n_fft/2 + 1 power-spectrum bins */
+    int32_t origin;       /* sample index, relative to the window's sample 0, of tap 0 of frame 0;
+                             -(n_fft/2) is torch.stft(center=True, pad_mode="constant") */
+    uint32_t n_weights;   /* floats of the band weights, 0..8192; 0 when n_mels == 0 */
+    uint32_t reserved[3]; /* 0 */
+} bnflac_mel_spec;        /* 32 bytes */
+
+/* flags of status word 0 of bnflac_gather_ranges_mel */
+enum { BNFLAC_MEL_BAD_WINDOW = 1, BNFLAC_MEL_BAD_BAND = 2 };
+
+/* The windows of a decoded selection as mel (or power) spectrogram planes [windows, planes, rows,
+ * frames] in one launch: bnflac_gather_ranges_f32, a windowed STFT, the power and a band-sparse
+ * projection, with the PCM read once and nothing but the feature tensor written.
+ * Tables.  The contract is in terms of the tables' values, whoever made them (bnflac_mel_design makes
+ * a Hann window, exact twiddles and HTK mel triangles).  With N = n_fft:
+ *   d_tab   float32, 16-byte aligned: the analysis window w[0 .. N), then N/2 twiddle pairs
+ *           C[k], S[k] at d_tab[N + 2k], d_tab[N + 2k + 1] for k = 0 .. N/2 - 1 (a design has
+ *           C[k] = cos(2 pi k / N), S[k] = sin(2 pi k / N); the factor applied is C[k] - i S[k]),
+ *           then the n_weights band weights: 2 N + n_weights floats.
+ *   d_bands uint32, n_mels + 1 pairs {first_bin, woff}: band m covers bins first_bin[m] ..
+ *           first_bin[m] + nb with nb = woff[m+1] - woff[m], its weights are weights[woff[m] ..].
+ *           It may be NULL when n_mels == 0.  A band is bad if woff[m+1] < woff[m], if woff[m+1] >
+ *           n_weights, or if first_bin[m] + nb > N/2 + 1.  A bad band is empty: its row is +0.0f,
+ *           and it is counted once per launch.  Whatever the tables hold, the call returns some
+ *           values and never faults: no trip count or address is a table value beyond that clamp.
+ * Layouts, the window check, planes and BNFLAC_F32_MONO are those of bnflac_gather_ranges_f32.  Per
+ * window s that passes the check, with n its nsamples: x[i] for 0 <= i < n is the float
+ * bnflac_gather_ranges_f32 specifies for sample frame i of the plane, x[i] = +0.0f for every other
+ * i.  Nothing outside the window is read.
+ * Frames.  Frame t starts at a_t = origin + t * hop (signed 64-bit).  n_valid = 0 when n == 0 or
+ * c = n - N/2 - origin < 0, else c / hop + 1: the frames whose centre lies at or before the window's
+ * end (origin = -N/2 gives torch's 1 + n / hop).  ncopy = min(n_valid, row_frames).
+ * Values of frame t < ncopy, every operation one float32 rounding, fmaf a fused multiply-add:
+ *   1. u[i] = w[i] * x[a_t + i], i = 0 .. N - 1                       (one product)
+ *   2. X = DFT_N(u) by the radix-2 decimation-in-time FFT on N complex points, no real-input
+ *      packing: v[brev(i)] = (u[i], +0.0f), brev the reversal of log2 N bits; then the stages
+ *      h = 1, 2, 4, .. N/2 in this order; in stage h, for every block base b (a multiple of 2h) and
+ *      j = 0 .. h - 1, with k = j * (N / 2h), A = v[b + j], B = v[b + j + h]:
+ *          pr = B.im * S[k];      tr = fmaf(B.re, C[k], pr)
+ *          pi = B.re * S[k];      ti = fmaf(B.im, C[k], -pi)
+ *          v[b + j]     = (A.re + tr, A.im + ti)
+ *          v[b + j + h] = (A.re - tr, A.im - ti)
+ *      The twiddles come from the table only, k = 0 included.  X[k] = v[k].
+ *   3. P[k] = fmaf(re, re, im * im) with (re, im) = X[k], k = 0 .. N/2.
+ *   4. n_mels == 0: row k is P[k].  Else row m: acc = +0.0f; for i = 0 .. nb - 1 ascending
+ *      acc = fmaf(weights[woff[m] + i], P[first_bin[m] + i], acc); the row's value is acc.
+ * No log: logf is not the same function on host and device, and the output is small enough for one
+ * elementwise op downstream.  Values are these bit for bit, on the device and in
+ * bnflac_gather_ranges_mel_host (tables without NaNs: a NaN's payload is not specified).
+ * Output: rows = n_mels ? n_mels : N/2 + 1.  Row r of plane c of window s starts at d_out +
+ * ((s * planes + c) * rows + r) * frame_pitch floats: its first ncopy floats are values, the rest up
+ * to row_frames are +0.0f, floats from row_frames to frame_pitch are not written.  A bad window's
+ * rows are all zero.
+ * d_status (device, 4 words): [0] bit 0 some bad window, bit 1 some bad band, [1] bad windows,
+ * [2] windows with n_valid > row_frames, [3] bad bands.  nstreams == 0 writes zeros.
+ * Refused (a negative return, the cause in bnflac_last_error(), nothing launched, nothing written):
+ * everything bnflac_gather_ranges_f32 refuses (layouts, channels outside 1..8, flag bits other than
+ * BNFLAC_F32_MONO, alignments, nstreams >= 2^30, null arguments); a null spec or d_tab; d_bands null
+ * with n_mels != 0; n_fft no power of two in 64..2048; hop outside 1..65535; n_mels above 256;
+ * n_weights above 8192, or not 0 with n_mels == 0; a non-zero reserved word; row_frames not below
+ * 2^31; frame_pitch < row_frames; d_tab not 16-byte aligned or d_bands not 4-byte aligned.
+ * spec is read on the host at call time.  Trip counts: the tiles of a row by row_frames, the planes
+ * and row passes by spec and the layout, the bins of a band by its clamped nb; a window enters through
+ * the check and through ncopy alone: the frames computed in a tile are min(ncopy - tile start, 32),
+ * a function of the window's nsamples bounded by row_frames and the same for every lane of a
+ * workgroup, so a window without valid frames costs only its zero stores.  No address depends on a
+ * window beyond the checked pcm_first.  Asynchronous on hip_stream, no host synchronisation, no
+ * allocation; the launch runs on ctx's device.  The output tile is 32 frames of one window. */
+BNFLAC_API int bnflac_gather_ranges_mel(bnflac_ctx *ctx, const uint8_t *d_pcm, uint64_t pcm_bytes, int out_format,
+                                        const bnflac_stream_params *sp, const bnflac_window *d_windows, uint32_t nstreams,
+                                        const bnflac_mel_spec *spec, const float *d_tab, const uint32_t *d_bands,
+                                        uint32_t row_frames, uint64_t frame_pitch, uint32_t flags, float *d_out,
+                                        uint32_t *d_status, void *hip_stream);
+
+/* The same rows and status from host memory, by the same code (csrc/bnf_mel.h); no GPU needed.
+ * Refuses what the device call refuses apart from pointer alignment (out, tab and bands need their
+ * type's).  0 or -1. */
+BNFLAC_API int bnflac_gather_ranges_mel_host(const uint8_t *pcm, uint64_t pcm_bytes, int out_format,
+                                             const bnflac_stream_params *sp, const bnflac_window *windows, uint32_t nstreams,
+                                             const bnflac_mel_spec *spec, const float *tab, const uint32_t *bands,
+                                             uint32_t row_frames, uint64_t frame_pitch, uint32_t flags, float *out,
+                                             uint32_t status[4]);
+
+/* Tables for bnflac_gather_ranges_mel.  Host only, no GPU.  Fills spec (origin = -(n_fft/2), the
+ * n_weights of the design), returns the floats tab needs, 2 n_fft + n_weights, and writes both tables
+ * when tab_cap is at least that and bands_cap at least 2 (n_mels + 1) words (0 for n_mels == 0), so
+ * a call with zero caps sizes them.  f_max <= 0 means sample_rate / 2.  In double, rounded to float:
+ *   w[i] = 0.5 - 0.5 cos(2 pi i / N)                          (the periodic Hann window)
+ *   C[k] = cos(2 pi k / N), S[k] = sin(2 pi k / N)
+ *   mel(f) = 2595 log10(1 + f / 700), hz(m) = 700 (10^(m / 2595) - 1);
+ *   f_j = hz(mel(f_min) + j (mel(f_max) - mel(f_min)) / (n_mels + 1)), j = 0 .. n_mels + 1;
+ *   bin k has frequency g_k = k sample_rate / N; the weight of bin k in band m is
+ *   max(0, min((g_k - f_m) / (f_m+1 - f_m), (f_m+2 - g_k) / (f_m+2 - f_m+1)))    (HTK, unnormalised):
+ * torchaudio.functional.melscale_fbanks(norm=None, mel_scale="htk") with its zero weights dropped.
+ * Band m holds the bins whose float32 weight is above 0, one run; a band without one has nb = 0 and
+ * first_bin 0.  The last pair is {0, n_weights}.
+ * A negative return for a zero rate, a null spec, sizes the gather refuses, f_min and f_max not
+ * 0 <= f_min < f_max <= sample_rate / 2, or a design over the gather's limits; then
+ * bnflac_last_error() states the n_mels and n_weights the design needs. */
+BNFLAC_API int64_t bnflac_mel_design(uint32_t sample_rate, uint32_t n_fft, uint32_t hop, uint32_t n_mels, double f_min,
+                                     double f_max, bnflac_mel_spec *spec, float *tab, uint64_t tab_cap, uint32_t *bands,
+                                     uint64_t bands_cap);
+
+/* The source window for frames [t0, t0 + n_frames) of a stream's own frame grid (frame t of the
+ * stream starts at sample spec->origin + t * hop), with the whole support of every frame.  Host only.
+ *   start = origin + t0 hop, first_sample = max(0, start), *origin = start - first_sample,
+ *   nsamples = max(0, start + (n_frames - 1) hop + N - first_sample)  (0 for n_frames = 0).
+ * A request of (stream, first_sample, nsamples) and a spec with this origin give the same values as
+ * columns [t0, t0 + n_frames) of the whole stream's result, bit for bit: the stream's start is
+ * supplied by the zero extension in front of the window, its end by the selection's clipping.
+ * 0, or -1 for a null argument, a spec the gather refuses or t0 + n_frames >= 2^31. */
+BNFLAC_API int bnflac_mel_request(const bnflac_mel_spec *spec, uint64_t t0, uint64_t n_frames, uint64_t *first_sample,
+                                  uint64_t *nsamples, int32_t *origin);
+
 /* ======================== Part 3: streaming reader ======================= */
 
 /* The fast path under FLACDecoder.Read (FLACDecoder.cs:124-205) and OpenAL's buffer fill
