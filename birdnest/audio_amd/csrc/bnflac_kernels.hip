@@ -1989,7 +1989,8 @@ __global__ void __launch_bounds__(DEC_LANES, 2) k_decode_seg(const uint32_t *__r
  * looks for a sync code right there).  A frame's footer makes the CRC-16 of the whole
  * frame zero, so without decoding anything: candidate j follows valid candidate i iff
  * CRC-16(bytes[c_i, c_j)) == 0 and j itself has a valid header (CRC-8) and subframe walk;
- * the first such j is taken.
+ * of these the first that can be the frame's end is taken (chain_succ_scan: not a sync code
+ * inside the part of frame i that k_parse walked, and a continuing number before another).
  * With P(y) = CRC-16(bytes[0, y)) and R(y) = P(y) * x^(8(N - y)) mod G (N = nbytes, x is
  * invertible mod G), CRC-16(bytes[a, b)) * x^(8(N - b)) = R(b) + R(a), so the test is the
  * equality of two per-candidate keys R(c).  R(c_j) is the XOR prefix over the gaps
@@ -2050,10 +2051,52 @@ __global__ void __launch_bounds__(1024) k_chain_keys(uint32_t *__restrict__ v, u
     }
 }
 
+/* The successor of valid candidate i among the candidates (i, jend).  Equal keys say that the
+ * CRC-16 from i closes at j and that j parses; that also holds at a decoy, a sync code inside
+ * frame i's own bytes in front of which the CRC-16 happens to be (or was made to be) zero.  Two
+ * further tests, both on fields k_parse already wrote and both only where the keys are equal, so
+ * that on encoder output the loop costs what it did:
+ *   - j lies at or past the start of frame i's last subframe (frame_off * 8 + sub_start[C - 1]):
+ *     k_parse has walked the frame that far, no frame ends before it;
+ *   - of the candidates left, the first whose header number continues i's (the next frame
+ *     number, or i's sample number plus its blocksize) wins over an earlier one whose number does
+ *     not.  libFLAC never compares the numbers, so a stream whose numbers do not continue (a
+ *     splice) keeps its links: when none of the next CHAIN_PAST candidates continues, the first
+ *     closing one is taken, as before.  The look past it is short on purpose.  From a frame
+ *     start the CRC-16 closes at every later frame start, so behind a splice a frame that
+ *     happens to carry the continuing number would be taken for the successor; a decoy and the
+ *     true end of its frame lie inside one subframe, a few accidental sync codes apart at most.
+ * What is left is a decoy in the last subframe whose number continues: DESIGN.md section 4. */
+#define CHAIN_PAST 16u /* candidates looked at past a closing one whose number does not continue */
+DEV int32_t chain_succ_scan(const uint32_t *__restrict__ key, const uint64_t *__restrict__ cand,
+                            const bnf_frame_info *__restrict__ info, uint32_t i, uint32_t jend) {
+    const uint32_t want = key[i];
+    int32_t first = -1;
+    uint64_t last_sub = 0, number = 0;
+    uint32_t blocksize = 0;
+    for (uint32_t j = i + 1; j < jend; j++) {
+        if (key[j] != want) continue;
+        if (blocksize == 0) { /* frame i's fields, read at the first closing candidate */
+            last_sub = info[i].frame_off * 8u + info[i].sub_start[(info[i].channels - 1u) & 7u];
+            number = info[i].number;
+            blocksize = info[i].blocksize; /* >= 1 for a parsed header */
+        }
+        if (cand[j] * 8u < last_sub) continue;
+        const uint64_t nj = info[j].number;
+        if (nj == number + 1u || nj == number + blocksize) return (int32_t)j;
+        if (first < 0) {
+            first = (int32_t)j;
+            jend = (uint32_t)min((uint64_t)jend, (uint64_t)j + 1u + CHAIN_PAST);
+        }
+    }
+    return first;
+}
+
 /* succ[i]: index of the candidate where frame i ends, -1 if none (or i is not valid);
  * head: the first valid candidate at or after first_off (atomicMin; preset to INT_MAX). */
 __global__ void __launch_bounds__(256) k_chain_succ(const uint64_t *__restrict__ cand, uint32_t ncand,
-                                                    const uint32_t *__restrict__ key, uint64_t first_off,
+                                                    const uint32_t *__restrict__ key,
+                                                    const bnf_frame_info *__restrict__ info, uint64_t first_off,
                                                     int32_t *__restrict__ succ, int32_t *__restrict__ head) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= ncand) return;
@@ -2062,11 +2105,7 @@ __global__ void __launch_bounds__(256) k_chain_succ(const uint64_t *__restrict__
     if (want & KEY_OK) {
         if (cand[i] >= first_off) atomicMin(head, (int32_t)i);
         const uint32_t jend = (uint32_t)min((uint64_t)ncand, (uint64_t)i + 1u + CHAIN_WIN);
-        for (uint32_t j = i + 1; j < jend; j++)
-            if (key[j] == want) {
-                s = (int32_t)j;
-                break;
-            }
+        s = chain_succ_scan(key, cand, info, i, jend);
     }
     succ[i] = s;
 }
@@ -2456,9 +2495,10 @@ __global__ void __launch_bounds__(256) k_ms_gap_crc(const uint8_t *__restrict__ 
  * wave's lowest such lane then speaks for all of them, one atomicMin per wave instead of
  * thousands on the same address (measured: 267 -> 19 us of this kernel on 64 C2 streams). */
 __global__ void __launch_bounds__(256) k_ms_succ(const uint64_t *__restrict__ cand, const uint32_t *__restrict__ ctl,
-                                                 const uint32_t *__restrict__ key, const int32_t *__restrict__ seg,
-                                                 const bnf_stream_desc *__restrict__ sd, const uint32_t *__restrict__ chi,
-                                                 int32_t *__restrict__ succ, int32_t *__restrict__ head) {
+                                                 const uint32_t *__restrict__ key, const bnf_frame_info *__restrict__ info,
+                                                 const int32_t *__restrict__ seg, const bnf_stream_desc *__restrict__ sd,
+                                                 const uint32_t *__restrict__ chi, int32_t *__restrict__ succ,
+                                                 int32_t *__restrict__ head) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     const bool live = i < ms_n(ctl); /* no early return: the wave votes below */
     const uint32_t want = live ? key[i] : 0u;
@@ -2479,11 +2519,7 @@ __global__ void __launch_bounds__(256) k_ms_succ(const uint64_t *__restrict__ ca
     int32_t r = -1;
     if (valid) {
         const uint32_t jend = (uint32_t)min((uint64_t)chi[s], (uint64_t)i + 1u + CHAIN_WIN);
-        for (uint32_t j = i + 1; j < jend; j++)
-            if (key[j] == want) {
-                r = (int32_t)j;
-                break;
-            }
+        r = chain_succ_scan(key, cand, info, i, jend);
     }
     succ[i] = r;
 }
@@ -4799,7 +4835,7 @@ hipError_t bnf_launch_chain(const uint8_t *bytes, uint64_t nbytes, const uint64_
     if (ncand) {
         hipLaunchKernelGGL(k_gap_crc, dim3((ncand + 3) / 4), dim3(256), 0, s, bytes, nbytes, cand, ncand, gap_crc);
         hipLaunchKernelGGL(k_chain_keys, dim3(1), dim3(1024), 0, s, gap_crc, ncand, info);
-        hipLaunchKernelGGL(k_chain_succ, g256, dim3(256), 0, s, cand, ncand, gap_crc, first_off, jump, head);
+        hipLaunchKernelGGL(k_chain_succ, g256, dim3(256), 0, s, cand, ncand, gap_crc, info, first_off, jump, head);
         for (uint32_t k = 0; k + 1 < levels; k++)
             hipLaunchKernelGGL(k_chain_jump, g256, dim3(256), 0, s, jump + (size_t)k * ncand,
                                jump + (size_t)(k + 1) * ncand, ncand);
@@ -4859,7 +4895,7 @@ hipError_t bnf_launch_chain_front(const uint8_t *bytes, uint64_t nbytes, const b
     hipLaunchKernelGGL(k_ms_keys_reduce, dim3(nbc), dim3(MS_SCAN), 0, s, w.key, ctl, w.csum);
     hipLaunchKernelGGL(k_ms_keys_sums, dim3(1), dim3(MS_SCAN), 0, s, w.csum, nbc);
     hipLaunchKernelGGL(k_ms_keys_apply, dim3(nbc), dim3(MS_SCAN), 0, s, w.key, ctl, w.csum, w.info, w.seg, sd);
-    hipLaunchKernelGGL(k_ms_succ, gc, t256, 0, s, w.cand, ctl, w.key, w.seg, sd, w.chi, w.jump, w.head);
+    hipLaunchKernelGGL(k_ms_succ, gc, t256, 0, s, w.cand, ctl, w.key, w.info, w.seg, sd, w.chi, w.jump, w.head);
     hipLaunchKernelGGL(k_ms_mark_heads, gs, t256, 0, s, w.head, S, ctl, w.mark);
     return hipGetLastError();
 }
